@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched lockstep gridworld step path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: it sets up, runs W warm-up steps, times exactly K bench steps on
+one primary ring, writes its outputs if --dump-outputs DIR is given and prints the line (`parity_sample_bit_exact` is null there).
+`--full` adds everything below that is not `value`: the five primary rings, the ring and oracle parity samples, the store-only
+probe, the other paths, the plain-ring spread, the outputs-once kernel, `sustained`, the weak-scaling line and the CPU baseline.
+--dump-outputs DIR writes what the primary path computed in its last bench step (see dump_outputs) for a fixed, seeded sample of
+the envs; the inputs are a function of the arguments alone, so two builds can be compared output for output.
 
 A bench "step" is one pass of the hot path over the whole env batch = one EPISODE for every env: `--lockstep-per-step`
 (default 100 = BoatRace's fixed horizon; SURVEY.md 8(d) states the measurement in whole 100-step episodes) lockstep
@@ -22,10 +29,10 @@ What is timed -- `--path`:
           records coalesce in L2: its rate is a fabric / Infinity-Cache write rate, not an HBM rate. Round 2's `value`.
   launch  one step-kernel launch per lockstep step, replayed from a hipGraph (state words through memory every step). Round
           1's `value` was this with one lockstep step per bench step.
-The default run reports the other two as secondary objects (`rewritten_in_place`, `per_step_launches`) and the outputs-once
+A --full run reports the other two as secondary objects (`rewritten_in_place`, `per_step_launches`) and the outputs-once
 kernel (`fused_rollout`: no per-step output exists), each with its own counter-based traffic figures.
 The ring's rate differs from allocation to allocation of the 3 GB, so the primary measurement is made
-`--rings` times (default 5: 15 GB of the 288), each on a FRESH ring of the same backing (the library's ring allocator `sgk_ring_alloc`: one virtual
+`--rings` times (default 5 with --full: 15 GB of the 288; 1 in a plain run), each on a FRESH ring of the same backing (the library's ring allocator `sgk_ring_alloc`: one virtual
 range mapped from 256 MiB physical chunks; `--ring-backing torch` for plain blocks), earlier rings held while the next is timed:
 `value` is the MEDIAN ring's whole-job rate, `value_min` / `value_max` and `primary_rings` give the spread, and every ring
 is also timed with the library's store-only probe (`sgk_ring_probe`: the kernel's stores and nothing else) so that
@@ -34,9 +41,9 @@ PLAIN rings (torch.empty) in the same process. Nothing is picked anywhere.
 
 Workload = BASELINE.json's metric config: BoatRace, 1 048 576 concurrent envs in the whole job at every GPU count (the batch
 shards by env id, one contiguous block per rank, no data-path collective; the only exchange is one int64 metrics all-reduce
-at the end of the timed region). At N > 1 a secondary object reports the weak-scaling form (1 048 576 envs on every GPU).
+at the end of the timed region). At N > 1 a --full run's secondary object reports the weak-scaling form (1 048 576 envs on every GPU).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects added.
+Rank 0 prints ONE JSON line (contract in the task statement) with a `roofline` object added (and `cpu_baseline` with --full).
 """
 import argparse
 import json
@@ -167,6 +174,47 @@ def ring_parity_sample(env_name, seed, base, ring, first_step, n_slices, block=5
         if not ((boards[sl, :m].cpu().numpy() == orc.boards()).all() and (recs[sl, :m].cpu().numpy() == np.asarray(rec)).all()):
             return False
     return True
+
+
+DUMP_MAX_ENVS = 4096        # --dump-outputs: envs of the seeded sample ...
+DUMP_BYTES = 48 << 20       # ... and at most this many bytes of per-env arrays (the rest is a few KB)
+
+
+def dump_outputs(dirname, env, path, ring, slice_next, last_steps, base, seed):
+    """--dump-outputs: what the primary path handed its caller in the last bench step, for a fixed sample of the envs (drawn from
+    `seed`, so two builds dump the same envs), as float32 / float64 .npy files. ring: the `last_steps` trajectory slices that step
+    wrote, oldest first -- trajectory_boards [S, m, cells], trajectory_records [S, m, 4] (reward, hidden reward, done, executed
+    action); own / launch: the env's own boards [m, cells] and step records [m, 4]. Every path: the episode state and last-episode
+    fields of the sampled envs, their global env ids and the env's metrics vector (the timed region's)."""
+    import numpy as np
+
+    n, cells = env.n_envs, env.n_cells
+    steps = min(last_steps, RING_SLICES) if path == "ring" else 1
+    m = max(1, min(n, DUMP_MAX_ENVS, DUMP_BYTES // (steps * (cells + 4) * 4 + 6 * 8)))
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+    out = {}
+    if path == "ring":
+        import torch
+
+        boards, recs = ring
+        order = [(slice_next - steps + k) % boards.shape[0] for k in range(steps)]
+        sl = torch.as_tensor(order, device=boards.device)
+        ti = torch.as_tensor(idx, device=boards.device)
+        out["trajectory_boards"] = boards.index_select(0, sl).index_select(1, ti).cpu().numpy().astype(np.float32)
+        out["trajectory_records"] = recs.index_select(0, sl).index_select(1, ti).cpu().numpy().astype(np.float32)
+    else:
+        out["boards"] = env.boards_host().reshape(n, -1)[idx].astype(np.float32)
+        out["step_records"] = env.step_records_host()[idx].astype(np.float32)
+    st, le = env.episode_state_host(), env.last_episode_host()
+    for k in ("episode_return", "hidden_return", "frame"):
+        out[k] = st[k][idx].astype(np.float64)
+    for k in ("last_return", "last_performance", "n_episodes"):
+        out[k] = le[k][idx].astype(np.float64)
+    out["env_index"] = (idx + base).astype(np.float64)
+    out["metrics"] = env.metrics().astype(np.float64)  # int64 counters and sums, far below 2**53
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def chunk_schedule(k):
@@ -664,8 +712,16 @@ def main():
     ap.add_argument("--ring-backing", choices=("ring", "torch"), default="ring",
                     help="memory of the PRIMARY trajectory ring: the library's ring allocator (sgk_ring_alloc: HIP virtual memory "
                          "management, 256 MiB physical chunks) or a plain torch.empty block")
-    ap.add_argument("--rings", type=int, default=5,
-                    help="how many fresh primary rings the timed region is repeated on (value = the median ring; path ring only)")
+    ap.add_argument("--rings", type=int, default=None,
+                    help="how many fresh primary rings the timed region is repeated on (value = the median ring; path ring only; "
+                         "default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 5 primary rings, ring + oracle parity samples, the store-only "
+                         "probe, the other paths, plain-ring spread, the outputs-once kernel, `sustained`, the weak-scaling line "
+                         "(N > 1) and the CPU baseline; without it a run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the primary path computed in its last bench step as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the envs, under 64 MB in all; rank 0's shard)")
     ap.add_argument("--no-weak-line", action="store_true", help="skip the secondary 1M-envs-per-GPU measurement at N > 1")
     ap.add_argument("--sustain-seconds", type=float, default=3.0,
                     help="after the timed region: the primary path's launches back to back for about this long (device time), as "
@@ -771,19 +827,22 @@ def run_rank(args):
     held = []
     total_steps = 0
     slice_next = [0]
-    n_primary = max(1, args.rings) if args.path == "ring" else 1
+    rings = args.rings if args.rings is not None else (5 if args.full else 1)
+    n_primary = max(1, rings) if args.path == "ring" else 1
     for r_i in range(n_primary):
         if args.path == "ring":
             ring, ring_alloc = alloc_ring(env, args.ring_backing)
             held.append(ring)
         slice_next, ring_start = [0], total_steps
         el, kms, gm_r = timed_steps(env, k_lock, w_lock, barrier, sdist.global_metrics, path=args.path, ring=ring, slice_next=slice_next)
+        if args.dump_outputs and rank == 0 and r_i == n_primary - 1:  # before the probe below zeroes the ring
+            dump_outputs(args.dump_outputs, env, args.path, ring, slice_next[0], min(L, k_lock), base, args.seed)
         per_rank = [x * 1e3 for x in gather_over_ranks(kms)]
         el, kms = max_over_ranks(el, kms)
         gpu_leg_ms += kms
         total_steps += w_lock + k_lock
         ok_r, probe_us = None, None
-        if ring is not None:  # the ring really holds the last steps' outputs (checked outside every clock) ...
+        if ring is not None and args.full:  # the ring really holds the last steps' outputs (checked outside every clock) ...
             ok_r = ring_parity_sample(args.env, args.seed, base, ring, total_steps - min(3, total_steps), min(3, total_steps),
                                       ring_start=ring_start)
             try:  # ... and what its memory takes from a kernel that only stores (zeros the ring: after the check)
@@ -797,10 +856,10 @@ def run_rank(args):
     mi = median_index([p["elapsed"] for p in primary])
     elapsed, kernel_ms, gm = primary[mi]["elapsed"], primary[mi]["kernel_ms"], primary[mi]["gm"]
     per_rank_device_us = primary[mi]["per_rank_device_us"]
-    ring_ok = None if args.path != "ring" else all(p["ring_ok"] for p in primary)
+    ring_ok = None if (args.path != "ring" or not args.full) else all(p["ring_ok"] for p in primary)
 
     secondary = {}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # the other two paths, same bracket, a bounded number of steps (device time per step is what these report; the host-clock
         # figure of the primary path is `value`)
         k2 = min(k_lock, 400)
@@ -835,7 +894,7 @@ def run_rank(args):
                 "traffic": fig["traffic"], "traffic_gbs": fig["traffic_gbs"], "traffic_frac": fig["traffic_frac"],
                 "note": notes[other]}
     ring_spread = None
-    if args.path == "ring" and not args.no_secondary:
+    if args.full and args.path == "ring" and not args.no_secondary:
         # what PLAIN rings (torch.empty: one hipMalloc block each) get in this very process, next to the primary rings' figures;
         # the earlier rings stay allocated while the next is timed
         spread_us = []
@@ -854,7 +913,7 @@ def run_rank(args):
                                "same kernel (device clock, max over ranks); the primary rings' own figures are in primary_rings"
                                % RING_SLICES}
     fused = None
-    if not args.no_fused:
+    if args.full and not args.no_fused:
         # same workload through the outputs-once rollout kernel (state in registers, boards materialised once per launch)
         env.synchronize()
         f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -876,10 +935,10 @@ def run_rank(args):
                  "roofline": issue_roofline(args.env, n_local, fused_steps, fms / 1e3, peak_now),
                  "note": "sgk_rollout_random: %d lockstep steps in ONE launch, outputs once at the end (no per-step observation "
                          "exists); rank 0's device time" % fused_steps}
-    ok, n_checked = parity_sample(env, args.env, args.seed, base, total_steps)
+    ok, n_checked = parity_sample(env, args.env, args.seed, base, total_steps) if args.full else (None, 0)
 
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         # The timed region is K x 100 lockstep steps = milliseconds of device work: a one-second busy sampler sees an idle GPU. The
         # same launches, back to back for seconds, on the last primary ring (rewritten lap after lap; after the parity sample: the
         # oracle does not follow these steps) -- whether the rate holds when the chip is warm and the clocks have settled.
@@ -896,7 +955,7 @@ def run_rank(args):
                              "(not part of `value`; not followed by the oracle)"}
 
     weak_line = None
-    if world > 1 and not weak and not args.no_weak_line:
+    if args.full and world > 1 and not weak and not args.no_weak_line:
         # secondary: the weak-scaling form (1 048 576 envs on EVERY GPU), same K / W, same bracket
         env.close()
         del ring, held
@@ -916,7 +975,7 @@ def run_rank(args):
         wenv.close()
 
     # every rank's parity sample counts: MIN over the ranks (also the last collective: every rank got here)
-    mine = bool(ok) and ring_ok is not False
+    mine = ok is not False and ring_ok is not False  # (None: not checked, a plain run)
     ok_all = mine if world == 1 else max_over_ranks(0.0 if mine else 1.0)[0] == 0.0  # (max of "failed" over the ranks)
     if world > 1:
         tdist.barrier()
@@ -956,6 +1015,7 @@ def run_rank(args):
         "vs_baseline": None,
         "dtype": "int8",
         "data": "synthetic",
+        "full": args.full,  # False: only the headline timing ran (no parity sample, probe, secondaries, baseline)
         "config": {
             "workload": "%s random-action rollout, %d concurrent envs in lockstep (%d per GPU), %s" % (args.env, n_total, n_local, what),
             "path": args.path,
@@ -989,7 +1049,7 @@ def run_rank(args):
         "gpu_leg_device_ms": gpu_leg_ms,
         "episodes_finished": gm.episodes,
         "mean_return": gm.meter("returns")["avg"], "mean_safety": gm.meter("safeties")["avg"],
-        "parity_sample_bit_exact": ok_all, "parity_sample_envs": n_checked, "parity_sample_ranks": world,
+        "parity_sample_bit_exact": ok_all if args.full else None, "parity_sample_envs": n_checked, "parity_sample_ranks": world,
         "ring_slices_checked_bit_exact": ring_ok,
     }
     out.update(secondary)
@@ -1006,11 +1066,11 @@ def run_rank(args):
         out["sustained"] = sustained
     if weak_line:
         out["weak_1m_per_gpu"] = weak_line
-    if not args.no_cpu_baseline and world == 1:  # a reported baseline of the N = 1 line only
+    if args.full and not args.no_cpu_baseline and world == 1:  # a reported baseline of the N = 1 line only
         out["cpu_baseline"] = cpu_baseline(args.env, args.seed)
     print(json.dumps(out))
     sys.stdout.flush()
-    return 0 if out["parity_sample_bit_exact"] else 3
+    return 0 if ok_all else 3
 
 
 if __name__ == "__main__":

@@ -108,7 +108,7 @@ def _check_contract(d, n_gpus, steps, warmup):
 
 @pytest.mark.gpu
 def test_bench_line_one_rank():
-    d = _line(["--steps", "3", "--warmup", "1", "--total-envs", "8192", "--lockstep-per-step", "100"])
+    d = _line(["--full", "--steps", "3", "--warmup", "1", "--total-envs", "8192", "--lockstep-per-step", "100"])
     _check_contract(d, 1, 3, 1)
     assert d["scaling"] == "weak" and d["config"]["envs_per_gpu"] == 8192 and d["roofline"]["steps_per_launch"] == 100
     cb = d["cpu_baseline"]
@@ -130,26 +130,69 @@ def test_bench_line_one_rank():
     assert abs(su["value"] - 8192 * su["lockstep_steps"] / su["seconds"]) <= 1e-6 * su["value"]
     assert su["device_us_per_lockstep_step"] <= su["us_per_lockstep_step"] and d["gpu_leg_device_ms"] >= su["device_us_per_lockstep_step"] * su["lockstep_steps"] / 1e3
     # another path as the primary one, and round 1's step definition
-    d2 = _line(["--steps", "40", "--warmup", "10", "--total-envs", "8192", "--path", "launch", "--lockstep-per-step", "1",
+    d2 = _line(["--full", "--steps", "40", "--warmup", "10", "--total-envs", "8192", "--path", "launch", "--lockstep-per-step", "1",
                 "--no-cpu-baseline", "--no-fused", "--sustain-seconds", "0.05"])
     _check_contract(d2, 1, 40, 10)
     assert d2["roofline"]["steps_per_launch"] == 1 and "cpu_baseline" not in d2 and d2["sustained"]["frac"] is None
     assert d2["kept_in_trajectory_ring"]["bound"] == "hbm" and d2["rewritten_in_place"]["value"] > 0
-    d3 = _line(["--steps", "3", "--warmup", "1", "--total-envs", "8192", "--path", "own", "--no-cpu-baseline", "--no-fused",
+    d3 = _line(["--full", "--steps", "3", "--warmup", "1", "--total-envs", "8192", "--path", "own", "--no-cpu-baseline", "--no-fused",
                 "--no-secondary", "--sustain-seconds", "0"])
     _check_contract(d3, 1, 3, 1)
     assert "sustained" not in d3
-    d4 = _line(["--steps", "3", "--warmup", "1", "--total-envs", "8192", "--ring-backing", "torch", "--no-cpu-baseline", "--no-fused",
+    d4 = _line(["--full", "--steps", "3", "--warmup", "1", "--total-envs", "8192", "--ring-backing", "torch", "--no-cpu-baseline", "--no-fused",
                 "--no-secondary"])
     _check_contract(d4, 1, 3, 1)
     assert d4["ring_allocation"]["backing"].startswith("torch.empty")
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_times_only_the_headline_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the run times the headline and nothing else (one primary ring, no parity sample, probe, secondary path or
+    baseline); --dump-outputs writes the same float arrays from run to run, and the dumped trajectory ring is the last bench step's
+    100 lockstep steps of the sampled envs, oldest first, as the oracle steps them."""
+    import numpy as np
+
+    from oracle import oracle as O
+
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--total-envs", "8192"]
+    d = _line(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["metric"].startswith("env-steps/sec") and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "int8" and (d["n_gpus"], d["steps"], d["warmup"]) == (1, 3, 1) and d["full"] is False
+    L = d["lockstep_steps_per_step"]
+    assert L == 100 and abs(d["value"] - 8192 * 3 * L / (d["ms_per_step"] * 3 / 1e3)) <= 1e-6 * d["value"]
+    assert d["parity_sample_bit_exact"] is None and d["ring_slices_checked_bit_exact"] is None and len(d["primary_rings"]) == 1
+    assert d["roofline"]["store_only_probe_us_per_step"] is None and d["episodes_finished"] == 8192 * 3
+    for k in ("cpu_baseline", "per_step_launches", "rewritten_in_place", "fused_rollout", "other_ring_allocations", "sustained",
+              "weak_1m_per_gpu"):
+        assert k not in d, k
+    _line(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"trajectory_boards.npy", "trajectory_records.npy", "metrics.npy"} <= set(names)
+    out, total = {}, 0
+    for nm in names:
+        x, y = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), nm
+        out[nm[:-4]], total = x, total + x.nbytes
+    assert total <= 64 << 20
+    idx = out["env_index"].astype(np.int64)
+    tb, tr = out["trajectory_boards"], out["trajectory_records"]
+    assert tb.shape[:2] == tr.shape[:2] == (100, len(idx)) and tr.shape[2] == 4 and len(np.unique(idx)) == len(idx)
+    seed = 0x5AFE
+    orc = O.EnvBatch("BoatRace-v0", 8192, seed=seed, env_begin=0)
+    orc.rollout(300, seed=seed, env_begin=0, t_begin=0, auto_reset=True)
+    for k in range(100):
+        rec = np.asarray(orc.rollout(1, seed=seed, env_begin=0, t_begin=300 + k, auto_reset=True)).reshape(8192, 4)
+        assert (tb[k] == orc.boards()[idx]).all() and (tr[k] == rec[idx]).all(), k
+    for f in ("episode_return", "hidden_return", "frame"):
+        assert (out[f] == orc.field(f)[idx]).all(), f
+    assert out["metrics"][O.M_EPISODES] == d["episodes_finished"]
+
+
+@pytest.mark.gpu
 def test_bench_line_two_ranks_on_one_gpu_shards_the_batch():
     """`python bench.py --gpus 2` starts its ranks itself (torch.distributed.run as a child, before any GPU call); the batch is
     cut into two contiguous env-id blocks; the line reports the whole job."""
-    d = _line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--total-envs", "8192", "--no-fused", "--sustain-seconds", "0.2"],
+    d = _line(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--total-envs", "8192", "--no-fused", "--sustain-seconds", "0.2"],
               env={"SGK_BENCH_BACKEND": "gloo", "SGK_BENCH_ONE_DEVICE": "1"})
     _check_contract(d, 2, 3, 1)
     assert d["scaling"] == "strong" and d["config"]["envs_per_gpu"] == 4096 and d["config"]["total_envs"] == 8192
@@ -178,7 +221,7 @@ def test_bench_exits_non_zero_when_the_librarys_communicator_is_missing():
 def test_bench_line_eight_ranks_dry_run_on_one_gpu():
     """The driver's 8-GPU launch, rehearsed on the one GPU of a test box (gloo collectives): eight ranks, eight contiguous env-id
     shards, one line with eight device times (what an 8-GPU node adds is RCCL and seven more devices, not control flow)."""
-    d = _line(["--gpus", "8", "--steps", "2", "--warmup", "1", "--total-envs", "16384", "--no-fused", "--no-weak-line", "--sustain-seconds", "0.2"],
+    d = _line(["--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--total-envs", "16384", "--no-fused", "--no-weak-line", "--sustain-seconds", "0.2"],
               env={"SGK_BENCH_BACKEND": "gloo", "SGK_BENCH_ONE_DEVICE": "1"}, timeout=900)
     _check_contract(d, 8, 2, 1)
     assert d["config"]["envs_per_gpu"] == 2048 and d["scaling"] == "strong" and d["episodes_finished"] == 16384 * 2

@@ -45,6 +45,23 @@ VARIANTS = [
 ]
 
 
+# every test_* function of tests/test_tables_cpu.py (none takes arguments), in definition order; stops at the first failure
+_RUN_TABLES_MODULE = """
+import sys, traceback
+import test_tables_cpu as T
+tests = [(k, f) for k, f in vars(T).items() if k.startswith("test_") and callable(f)]
+assert len(tests) >= 9, [k for k, _ in tests]
+for name, fn in tests:
+    try:
+        fn()
+    except BaseException:
+        traceback.print_exc()
+        print("FAILED", name)
+        sys.exit(1)
+    print("passed", name)
+"""
+
+
 def _build_pair(tmp, switch, value):
     defs = "-D%s=%s" % (switch, value)
     host = hostlib.build(out=os.path.join(tmp, "libsgk_host.so"), defs=defs)
@@ -59,12 +76,14 @@ def test_product_tables_and_oracle_agree_under_the_alternative_reading(tmp_path,
     host, orc = _build_pair(str(tmp_path), switch, value)
     # IslandNavigation's '#' = 0 makes wall and water ONE value with two colours: a board of values cannot be coloured then
     skip_palette = "IslandNavigation-v0" if switch == "SGK_ISLAND_VALUE_WALL" else ""
+    paths = [ROOT, os.path.join(ROOT, "safe-grid-agents_amd"), os.path.join(ROOT, "tests")]
     env = dict(os.environ, SGK_HOST_LIB=host, SGK_ORACLE_SO=orc, SGK_WALK_EXAMPLES="40", SGK_SKIP_PALETTE=skip_palette,
-               PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "safe-grid-agents_amd"), os.path.join(ROOT, "tests")]))
-    # the variant pair through the whole table-vs-engine module (a fresh interpreter: the libraries are process-wide)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
-                        os.path.join(ROOT, "tests", "test_tables_cpu.py")], env=env, cwd=str(tmp_path), capture_output=True,
-                       text=True, timeout=600)
+               PYTHONPATH=os.pathsep.join(paths + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
+    # the variant pair through the whole table-vs-engine module, in a fresh interpreter (the libraries are process-wide): a bare
+    # python that calls every test of the module in order -- no second pytest, whose configuration, plugins and temporary
+    # directories would come from wherever and however the outer run was started
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", _RUN_TABLES_MODULE],
+                       env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, "%s=%s\n%s\n%s" % (switch, value, r.stdout[-3000:], r.stderr[-2000:])
     # and the switch does what it says to the product's tables: exactly the named levels change
     base, var = hostlib.load(), hostlib.load(host)

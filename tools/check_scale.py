@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pass / fail verdict for `bench.py --gpus {1,2,4,8}` lines against BASELINE.md section 10 (the prediction committed BEFORE any
+"""Pass / fail verdict for `bench.py --full --gpus {1,2,4,8}` lines against BASELINE.md section 10 (the prediction committed BEFORE any
 multi-GPU run: no node with more than one GPU was ever available to the build).
 
     python tools/check_scale.py line_n1.json line_n2.json ...        (files holding bench.py's ONE JSON line, or a driver record
@@ -86,7 +86,9 @@ def check(line, allow_collective=()):
     else:
         res.append(("episodes", None, "not in this record"))
     slices = line.get("ring_slices_checked_bit_exact")
-    if "parity_sample_bit_exact" in line:
+    if line.get("full") is False:  # a plain run times the headline only: nothing was checked
+        res.append(("parity", None, "not checked (a run without --full)"))
+    elif "parity_sample_bit_exact" in line:
         res.append(("parity", bool(line.get("parity_sample_bit_exact")) and slices is not False,
                     "parity_sample_bit_exact %r, ring slices %r" % (line.get("parity_sample_bit_exact"), slices)))
     else:

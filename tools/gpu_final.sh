@@ -8,12 +8,12 @@ T=${1:-r06}; O=gpurun_out/${T}_final; mkdir -p $O
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -1 $O/smoke.log
 timeout 2400 python -m pytest tests -m gpu -q --timeout=900 > $O/pytest_gpu.log 2>&1; echo "rc=$?" >> $O/pytest_gpu.log; tail -8 $O/pytest_gpu.log | grep -v "RCCL\|HIP ver\|ROCm\|Hostname\|Librccl" | cut -c1-300
 # the driver's bench command, three processes
-for i in 1 2 3; do SGK_BENCH_TRACE=1 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags_$i.log 2> $O/bench_driver_flags_$i.err; tail -1 $O/bench_driver_flags_$i.log | cut -c1-200; done
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --path own --no-cpu-baseline > $O/bench_path_own.log 2>&1
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --path launch --no-cpu-baseline > $O/bench_path_launch.log 2>&1
+for i in 1 2 3; do SGK_BENCH_TRACE=1 timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags_$i.log 2> $O/bench_driver_flags_$i.err; tail -1 $O/bench_driver_flags_$i.log | cut -c1-200; done
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --path own --no-cpu-baseline > $O/bench_path_own.log 2>&1
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --path launch --no-cpu-baseline > $O/bench_path_launch.log 2>&1
 # the multi-rank control flow end to end on the one GPU of the box: ranks share GPU 0, gloo collectives (RCCL needs one GPU per rank)
-SGK_BENCH_BACKEND=gloo SGK_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --no-fused > $O/bench_2rank_one_gpu_gloo.log 2>&1; tail -1 $O/bench_2rank_one_gpu_gloo.log | cut -c1-300
-SGK_BENCH_BACKEND=gloo SGK_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 5 --warmup 2 --no-fused --no-weak-line --no-secondary > $O/bench_8rank_one_gpu_gloo.log 2>&1; tail -1 $O/bench_8rank_one_gpu_gloo.log | cut -c1-300
+SGK_BENCH_BACKEND=gloo SGK_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-fused > $O/bench_2rank_one_gpu_gloo.log 2>&1; tail -1 $O/bench_2rank_one_gpu_gloo.log | cut -c1-300
+SGK_BENCH_BACKEND=gloo SGK_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 8 --steps 5 --warmup 2 --no-fused --no-weak-line --no-secondary > $O/bench_8rank_one_gpu_gloo.log 2>&1; tail -1 $O/bench_8rank_one_gpu_gloo.log | cut -c1-300
 # BASELINE configs 2-4 (roofline + cpu_baseline each), their counters; config 3's kernel under the SQ counters
 bash tools/gpu_configs.sh ${T}_final > $O/gpu_configs.out 2>&1; tail -12 $O/gpu_configs.out | cut -c1-300
 bash tools/gpu_pmc_tabq.sh ${T}_final final > $O/gpu_pmc_tabq.out 2>&1; tail -4 $O/gpu_pmc_tabq.out | cut -c1-300
@@ -36,7 +36,7 @@ timeout 600 python tools/bench_ppo.py cnn 2>&1 | grep -v amdgpu.ids > $O/ppo_cnn
 timeout 900 bash tools/gpu_pmc_convq.sh > $O/convq_pmc.out 2>&1; cp gpurun_out/pmc_convq_summary.json $O/convq_pmc_summary.json 2>/dev/null
 for f in $(find gpurun_out/convq_trace -name "*kernel_stats.csv" 2>/dev/null); do cp $f $O/convq_kernel_stats.csv; head -3 $f | cut -c1-200; done
 export SGK_NO_BUILD=1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-fused --sustain-seconds 0 > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-fused --sustain-seconds 0 > $O/bench_under_rocprof.log 2>&1
 for f in $(find $O/prof -name "*kernel_stats.csv"); do head -6 $f | cut -c1-200; cp $f $O/bench_kernel_stats.csv; done
 rm -rf $O/prof
 # config 2's kernel (one step_kernel launch per lockstep step) and config 4's learner (dqn_sgd_kernel) under the kernel trace
