@@ -532,6 +532,51 @@ typedef struct sgk_ppo_learner {
   double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
 } sgk_ppo_learner;
 SGK_API int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *learner);
+/* ---- PPOBaseAgent.learn (reference policy_base.py:64-131) for PPOCNNAgent (policy_cnn.py:17-81) on the device ------------ */
+/* All `n_epochs` minibatch updates of one learn() call, three launches per epoch enqueued by this one call (forward, backward, Adam;
+ * no allocation, no host synchronisation, no float atomics: deterministic, and a captured replay equals the eager call bit for bit).
+ * Per epoch `batch` rows -- the caller's, or sgk_ppo_epochs' draw (counter RNG stream 5 keyed by the Adam step; the same rows for the
+ * same rollout and step) -- the current network
+ *     trunk  = relu(conv3x3(relu(conv3x3(x, 1 -> C)), C -> C)) + conv1x1(x, 1 -> C)              policy_cnn.py:19-44, 70
+ *     actor  = linear(flatten(relu(conv3x3(trunk, C -> C))), C * n_cells -> 4)                   policy_cnn.py:46-55, 72-74
+ *     critic = linear(flatten(relu(conv3x3(trunk, C -> C))), C * n_cells -> 1)                   policy_cnn.py:57-64, 76-79
+ * and the old policy's trunk + actor, advantages r - V(s) normalised over the minibatch (unbiased std, NOT detached: the policy loss
+ * also reaches the critic), clipped surrogate + critic_coeff * mse_loss - entropy_bonus * entropy (policy_base.py:82-106), backward
+ * through both heads, the residual split, conv2 and conv1, Adam (torch defaults, no amsgrad). n_channels 4, 5 (the reference default)
+ * or 8, n_layers 2, four actions, boards of 5x5, 6x5, 6x6, 6x8, 7x7, 7x8 or 7x9 cells, 2 <= batch <= 64. Device pointers; float32.
+ *   rollout     as for sgk_ppo_learner (sgk_convq_rollout's outputs)
+ *   params      the 14 current tensors in torch layout and registration order, UPDATED IN PLACE: network.0.0 weight [C][1][3][3] /
+ *               bias, network.1.0.0 [C][C][3][3] / [C], bottleneck [C][1][1][1] / [C], actor_cnn.0 [C][C][3][3] / [C], actor_linear
+ *               [4][C * n_cells] / [4], critic_cnn.0 [C][C][3][3] / [C], critic_linear [1][C * n_cells] / [1]
+ *   m, v        Adam's exp_avg / exp_avg_sq of each of them
+ *   old_params  the old policy's first ten tensors (trunk, bottleneck, actor path), read in place
+ *   step        Adam's step counter (int64, device), advanced by n_epochs
+ *   stats_out   float [n_epochs][3]: policy loss, value loss, entropy of each epoch before its update; or NULL
+ *   rows        int64 [n_epochs][batch] rows step * n_trajectories + trajectory replacing the draws; or NULL
+ *   rows_out    int64 [n_epochs][batch] receives the rows each epoch used; or NULL
+ *   workspace   sgk_ppo_cnn_workspace_bytes(h, n_channels, batch) bytes of device memory, 8-byte aligned, owned by the caller
+ * fp32 in another summation order than MIOpen / rocBLAS: equal to torch's updates to fp32 tolerance, not bit for bit. */
+typedef struct sgk_ppo_cnn_learner {
+  const int8_t *states;
+  const uint8_t *actions;
+  const float *returns;
+  const int32_t *lengths;
+  int32_t horizon, n_channels, batch, n_epochs;
+  int64_t n_trajectories;
+  float *params[14];
+  float *m[14], *v[14];
+  const float *old_params[10];
+  int64_t *step;
+  float *stats_out;
+  const int64_t *rows;
+  int64_t *rows_out;
+  void *workspace;
+  double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
+} sgk_ppo_cnn_learner;
+SGK_API int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *learner);
+/* The workspace sgk_ppo_cnn_epochs needs on this handle's level, in bytes; -1 (sgk_last_error says why) for an unsupported n_channels,
+ * board shape or batch. */
+SGK_API int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch);
 /* ReplayBuffer.add for every env (reference contain.py:15-17 via value.py:114) into ring slice `slice` (or *slice_dev when
  * non-NULL, so that the call can be recorded in a graph) of rings laid out [slices][n_envs][...]: phase 0, called before
  * sgk_step, stores the current boards as the transitions' state; phase 1, called after it, stores the boards as successor

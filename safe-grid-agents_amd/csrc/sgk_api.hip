@@ -1044,6 +1044,50 @@ int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try {
   return SGK_OK;
 } SGK_CATCH_STATUS
 
+int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch) try {
+  if (!h) return (int64_t)fail(SGK_ERR_INVALID, "handle is NULL");
+  const int H = h->sh.rules_host.height, W = h->sh.rules_host.width;
+  if (!sgk::ppo_cnn_shape_supported(H, W, n_channels) || batch < 2 || batch > 64) {
+    fail(SGK_ERR_INVALID, "sgk_ppo_cnn_workspace_bytes needs n_channels 4, 5 or 8, 2 <= batch <= 64 and a board of 5x5, 6x5, 6x6, 6x8, 7x7, "
+                          "7x8 or 7x9 (this level: %dx%d)", H, W);
+    return -1;
+  }
+  return (int64_t)sgk::ppo_cnn_workspace_bytes(H, W, n_channels, batch);
+} SGK_CATCH_VALUE(-1)
+
+int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try {
+  SGK_CHECK_HANDLE(h);
+  if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
+  const void *need[] = {L->states, L->actions, L->returns, L->lengths, L->step, L->workspace};
+  for (const void *p : need)
+    if (!p) return fail(SGK_ERR_INVALID, "NULL pointer in sgk_ppo_cnn_learner");
+  for (int i = 0; i < 14; ++i)
+    if (!L->params[i] || !L->m[i] || !L->v[i]) return fail(SGK_ERR_INVALID, "NULL parameter or Adam state in sgk_ppo_cnn_learner");
+  for (int i = 0; i < 10; ++i)
+    if (!L->old_params[i]) return fail(SGK_ERR_INVALID, "NULL old-policy tensor in sgk_ppo_cnn_learner");
+  const int H = h->sh.rules_host.height, W = h->sh.rules_host.width;
+  if (!sgk::ppo_cnn_shape_supported(H, W, L->n_channels))
+    return fail(SGK_ERR_INVALID, "sgk_ppo_cnn_epochs needs n_channels 4, 5 (the reference default) or 8 and a board of 5x5, 6x5, 6x6, 6x8, "
+                                 "7x7, 7x8 or 7x9 (this level: %dx%d, n_channels %d)", H, W, L->n_channels);
+  if (L->batch < 2 || L->batch > 64 || L->n_epochs < 1 || L->horizon < 1 || L->n_trajectories < 1 || L->n_trajectories >= (1ll << 31))
+    return fail(SGK_ERR_INVALID, "sgk_ppo_cnn_epochs needs 2 <= batch <= 64, n_epochs >= 1, horizon >= 1, 1 <= n_trajectories < 2^31");
+  sgk::PpoCnnLearner d;
+  d.states = L->states; d.actions = L->actions; d.returns = L->returns; d.lengths = L->lengths;
+  d.horizon = L->horizon; d.n_channels = L->n_channels; d.batch = L->batch; d.n_epochs = L->n_epochs;
+  d.n_trajectories = L->n_trajectories;
+  for (int i = 0; i < 14; ++i) { d.p[i] = L->params[i]; d.m[i] = L->m[i]; d.v[i] = L->v[i]; }
+  for (int i = 0; i < 10; ++i) d.o[i] = L->old_params[i];
+  d.step = reinterpret_cast<long long *>(L->step);
+  d.stats_out = L->stats_out;
+  d.rows = reinterpret_cast<const long long *>(L->rows);
+  d.rows_out = reinterpret_cast<long long *>(L->rows_out);
+  d.workspace = L->workspace;
+  d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
+  d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
+  SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream));
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
                            int64_t n_trajectories, int32_t t_max, double discount) try {
   SGK_CHECK_HANDLE(h);

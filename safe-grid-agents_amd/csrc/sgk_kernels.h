@@ -161,6 +161,27 @@ struct PpoLearner {
 };
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden);
 hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st);
+// PPOBaseAgent.learn for PPOCNNAgent (sgk_ppo_cnn.hip): tensors in registration order (network.0.0, network.1.0.0, bottleneck,
+// actor_cnn.0, actor_linear, critic_cnn.0, critic_linear; weight then bias), the old policy's first ten
+struct PpoCnnLearner {
+  const int8_t *states;
+  const uint8_t *actions;
+  const float *returns;
+  const int32_t *lengths;
+  int horizon, n_channels, batch, n_epochs;
+  int64_t n_trajectories;
+  float *p[14], *m[14], *v[14];
+  const float *o[10];
+  long long *step;
+  float *stats_out;
+  const long long *rows;
+  long long *rows_out;
+  void *workspace;
+  double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
+};
+bool ppo_cnn_shape_supported(int height, int width, int n_channels);
+size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch);
+hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st);
 hipError_t launch_discounted_returns(const Shard &sh, const float *rewards, const int32_t *lengths, const float *gamma_pow,
                                      float *returns, int64_t n, int t_max, hipStream_t st);
 hipError_t launch_render_rgb(const Shard &sh, uint8_t *dst, hipStream_t st);

@@ -79,6 +79,16 @@ class SgkPpoLearner(ctypes.Structure):
                 + [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "clipping", "critic_coeff", "entropy_bonus")])
 
 
+class SgkPpoCnnLearner(ctypes.Structure):
+    _V14, _V10 = ctypes.c_void_p * 14, ctypes.c_void_p * 10
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("states", "actions", "returns", "lengths")]
+                + [(k, ctypes.c_int32) for k in ("horizon", "n_channels", "batch", "n_epochs")]
+                + [("n_trajectories", ctypes.c_int64)]
+                + [("params", _V14), ("m", _V14), ("v", _V14), ("old_params", _V10)]
+                + [(k, ctypes.c_void_p) for k in ("step", "stats_out", "rows", "rows_out", "workspace")]
+                + [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "clipping", "critic_coeff", "entropy_bonus")])
+
+
 def build(force=False, verbose=False):
     """Compile libsgk.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))]
@@ -146,6 +156,8 @@ _SIGNATURES = {
     "sgk_step_store": (ctypes.c_int, [_V, _V, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
     "sgk_reset_done_store": (ctypes.c_int, [_V, ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
     "sgk_ppo_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner)]),
+    "sgk_ppo_cnn_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner)]),
+    "sgk_ppo_cnn_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
     "sgk_replay_store": (ctypes.c_int, [_V, ctypes.c_int32, _V, ctypes.c_int32, ctypes.c_int64, _V, _V, _V, _V, _V, _V]),
     "sgk_categorical_sample": (ctypes.c_int, [_V, _V, ctypes.c_uint64, _V, _V]),
     "sgk_policy_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_uint64, _V, _V, _V]),

@@ -797,6 +797,20 @@ class BatchedGridworldEnv:
         _lib.check(self.lib.sgk_ppo_epochs(self._h.ptr, ctypes.byref(learner)))
         self._sync_lib_to_torch()
 
+    def ppo_cnn_epochs(self, learner):
+        """All epochs of one PPOCNNAgent learn() call on the device, three HIP launches per epoch (sgk_ppo_cnn_epochs); `learner` is a
+        filled _lib.SgkPpoCnnLearner whose device pointers (the workspace among them) the caller keeps alive."""
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_ppo_cnn_epochs(self._h.ptr, ctypes.byref(learner)))
+        self._sync_lib_to_torch()
+
+    def ppo_cnn_workspace_bytes(self, n_channels, batch):
+        """Bytes of device workspace sgk_ppo_cnn_epochs needs on this level with n_channels and batch rows; SgkError when unsupported."""
+        nbytes = self.lib.sgk_ppo_cnn_workspace_bytes(self._h.ptr, int(n_channels), int(batch))
+        if nbytes < 0:
+            _lib.check(_lib.ERR_INVALID)
+        return int(nbytes)
+
     def discounted_returns(self, rewards, discount, lengths=None, out=None):
         """PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186) for a batch: rewards float32
         [n_trajectories, T] on this GPU (lengths int32 [n_trajectories] optional) -> returns of the same shape, with the

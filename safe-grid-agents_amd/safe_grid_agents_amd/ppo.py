@@ -241,13 +241,17 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
       * any other body (other depths / widths): the torch forward on the float32 observation (sgk_obs_f32) followed by
         sgk_categorical_sample on the logits.
 
+    learn() is one launch for the ppo-mlp shapes above with 2 <= batch_size <= 64 (sgk_ppo_epochs); with fused_conv_learn=True
+    (off by default) the ppo-cnn shapes with 2 <= batch_size <= 64 learn on the device as well (sgk_ppo_cnn_epochs: three launches
+    per epoch); every other case runs torch autograd.
+
     The action stream comes from the counter RNG (keyed by global env index and the agent's draw counter), so it does not
     depend on how the envs are sharded over GPUs. `net` is a PPOMLPAgent / PPOCNNAgent on the env's device: its
     surrogate_loss / sync / old_policy are used as they are."""
 
     reads_boards = True  # acts on the materialised cells (batched_default_eval must keep writing them)
 
-    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True):
+    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True, fused_conv_learn=False):
         import types
 
         cfg = types.SimpleNamespace(**vars(args))
@@ -297,6 +301,9 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             self.n_channels = int(args.n_channels)
             self._cw_old, self._cw = self._conv_weights(self.net.old_policy), self._conv_weights(self.net)
             self.graph_gather = False  # four launches per step: calling them costs less than a graph replay's fixed share (33.6 vs 35.7 us)
+        # ppo-cnn's learn() on the device (sgk_ppo_cnn_epochs) where that kernel applies; Adam's state and its workspace then live in self._pl
+        if bool(fused_conv_learn) and self.fused_conv and 2 <= self.batch_size <= 64:
+            self.fused_learn = True
 
     @staticmethod
     def _conv_weights(net):
@@ -456,6 +463,22 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         return [l1.weight.data, l1.bias.data, l2.weight.data, l2.bias.data, net.actor.weight.data, net.actor.bias.data,
                 net.critic.weight.data, net.critic.bias.data]
 
+    def _flat_rows(self, rollout, rows, rows_out):
+        """The fused learners' `rows` (one tensor of (t, env)-ordered valid-pair indices per epoch) as flat rows t * N + env, int64
+        [epochs, batch_size] on the device, or None; `rows_out` checked."""
+        chk = self.env._check
+        keep = None
+        if rows is not None:
+            T, n = rollout.actions.shape
+            valid = torch.arange(T, device=self.device).unsqueeze(1) < rollout.lengths.unsqueeze(0)
+            t_ix, n_ix = valid.nonzero(as_tuple=True)
+            flat = t_ix * n + n_ix
+            keep = torch.stack([flat[torch.as_tensor(r, device=self.device)] for r in rows]).to(torch.int64).contiguous()
+            chk(keep, "rows", shape=(self.epochs, self.batch_size), dtypes=("int64",))
+        if rows_out is not None:  # int64 [epochs, batch_size] on the device: receives the flat rows t * N + env used
+            chk(rows_out, "rows_out", shape=(self.epochs, self.batch_size), dtypes=("int64",))
+        return keep
+
     def _learn_fused(self, rollout, rows=None, rows_out=None):
         """`epochs` updates by sgk_ppo_epochs: sampling, both forwards, loss, backward and Adam of every epoch in one
         kernel. The transposed weight copies it reads are refreshed from the torch parameters first (four small copies), so
@@ -492,22 +515,78 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         L.ow1t, L.ob1, L.ow2t, L.ob2 = ptr(self._fw["w1t"]), ptr(self._fw["b1"]), ptr(pl["ow2t"]), ptr(self._fw["b2"])
         L.owa, L.oba = ptr(old.actor.weight.data), ptr(old.actor.bias.data)
         L.step, L.stats_out = ptr(pl["step"]), ptr(self._stats)
-        keep = None
-        if rows is not None:  # one tensor of (t, env)-ordered valid-pair indices per epoch -> flat rows t * N + env
-            valid = torch.arange(T, device=self.device).unsqueeze(1) < rollout.lengths.unsqueeze(0)
-            t_ix, n_ix = valid.nonzero(as_tuple=True)
-            flat = t_ix * n + n_ix
-            keep = torch.stack([flat[torch.as_tensor(r, device=self.device)] for r in rows]).to(torch.int64).contiguous()
-            chk(keep, "rows", shape=(self.epochs, self.batch_size), dtypes=("int64",))
+        keep = self._flat_rows(rollout, rows, rows_out)
+        if keep is not None:
             L.rows = ptr(keep)
-        if rows_out is not None:  # int64 [epochs, batch_size] on the device: receives the flat rows t * N + env used
-            chk(rows_out, "rows_out", shape=(self.epochs, self.batch_size), dtypes=("int64",))
+        if rows_out is not None:
             L.rows_out = ptr(rows_out)
         g = self.net.optim.param_groups[0]
         L.lr, (L.beta1, L.beta2), L.eps = float(g["lr"]), g["betas"], float(g["eps"])
         L.clipping, L.critic_coeff, L.entropy_bonus = float(self.net.clipping), float(self.net.critic_coeff), float(self.net.entropy_bonus)
         self.env.ppo_epochs(L)
         return keep
+
+    # PPOCNNAgent's parameters in registration order: what sgk_ppo_cnn_epochs updates (all 14) and reads of the old policy (the first 10)
+    CNN_PARAMS = ("network.0.0.weight", "network.0.0.bias", "network.1.0.0.weight", "network.1.0.0.bias", "bottleneck.weight",
+                  "bottleneck.bias", "actor_cnn.0.weight", "actor_cnn.0.bias", "actor_linear.weight", "actor_linear.bias",
+                  "critic_cnn.0.weight", "critic_cnn.0.bias", "critic_linear.weight", "critic_linear.bias")
+
+    def _learn_fused_cnn(self, rollout, rows=None, rows_out=None):
+        """`epochs` updates of the conv body by sgk_ppo_cnn_epochs: sampling, both forwards, loss, backward and Adam of every epoch
+        on the device, three launches per epoch. The kernels read and update the torch parameters in place and read the old
+        policy's in place; Adam's state, the step counter and the workspace are allocated once (fixed addresses: the call can be
+        recorded in a graph when `rows` is None)."""
+        L, keep = self._cnn_learner(rollout, rows, rows_out)
+        self.env.ppo_cnn_epochs(L)
+        return keep
+
+    def _cnn_learner(self, rollout, rows=None, rows_out=None):
+        """The filled _lib.SgkPpoCnnLearner of one _learn_fused_cnn call, and the flat rows tensor it points to (keep it alive)."""
+        from . import _lib
+        import ctypes
+
+        cur, old = dict(self.net.named_parameters()), dict(self.net.old_policy.named_parameters())
+        own = [cur[k].data for k in self.CNN_PARAMS]
+        olds = [old[k].data for k in self.CNN_PARAMS[:10]]
+        if self._pl is None:
+            nbytes = self.env.ppo_cnn_workspace_bytes(self.n_channels, self.batch_size)
+            self._pl = {"m": [torch.zeros_like(p) for p in own], "v": [torch.zeros_like(p) for p in own],
+                        "step": torch.zeros(1, dtype=torch.int64, device=self.device),
+                        "ws": torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
+        pl = self._pl
+        T, n = rollout.actions.shape
+        L = _lib.SgkPpoCnnLearner()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        chk = self.env._check  # ValueError for a tensor of the wrong device / dtype / shape: the kernels take raw pointers
+        chk(rollout.states, "rollout.states", shape=(T, n, self.env.n_cells), dtypes=("int8",))
+        chk(rollout.actions, "rollout.actions", shape=(T, n), dtypes=("uint8",))
+        chk(rollout.returns, "rollout.returns", shape=(n, T), dtypes=("float32",))
+        chk(rollout.lengths, "rollout.lengths", shape=(n,), dtypes=("int32",))
+        L.states, L.actions, L.returns, L.lengths = ptr(rollout.states), ptr(rollout.actions), ptr(rollout.returns), ptr(rollout.lengths)
+        L.horizon, L.n_channels, L.batch, L.n_epochs, L.n_trajectories = T, self.n_channels, self.batch_size, self.epochs, n
+        C, cells = self.n_channels, self.env.n_cells
+        sizes = (9 * C, C, 9 * C * C, C, C, C, 9 * C * C, C, 4 * C * cells, 4, 9 * C * C, C, C * cells, 1)  # what the kernels index
+        for i, k in enumerate(self.CNN_PARAMS):
+            chk(own[i], "parameter " + k, numel=sizes[i], dtypes=("float32",))
+            chk(pl["m"][i], "Adam exp_avg of " + k, numel=sizes[i], dtypes=("float32",))
+            chk(pl["v"][i], "Adam exp_avg_sq of " + k, numel=sizes[i], dtypes=("float32",))
+            L.params[i], L.m[i], L.v[i] = own[i].data_ptr(), pl["m"][i].data_ptr(), pl["v"][i].data_ptr()
+        for i, k in enumerate(self.CNN_PARAMS[:10]):
+            chk(olds[i], "old policy " + k, numel=sizes[i], dtypes=("float32",))
+            L.old_params[i] = olds[i].data_ptr()
+        chk(pl["step"], "step", shape=(1,), dtypes=("int64",))
+        chk(self._stats, "stats", shape=(self.epochs, 3), dtypes=("float32",))
+        chk(pl["ws"], "workspace", numel=self.env.ppo_cnn_workspace_bytes(self.n_channels, self.batch_size), dtypes=("uint8",))
+        L.step, L.stats_out, L.workspace = ptr(pl["step"]), ptr(self._stats), ptr(pl["ws"])
+        keep = self._flat_rows(rollout, rows, rows_out)
+        if keep is not None:
+            L.rows = ptr(keep)
+        if rows_out is not None:
+            L.rows_out = ptr(rows_out)
+        g = self.net.optim.param_groups[0]
+        L.lr, (L.beta1, L.beta2), L.eps = float(g["lr"]), g["betas"], float(g["eps"])
+        L.clipping, L.critic_coeff, L.entropy_bonus = float(self.net.clipping), float(self.net.critic_coeff), float(self.net.entropy_bonus)
+        return L, keep
 
     def _log_stats(self, history):
         stats = self._stats.cpu().numpy()
@@ -524,7 +603,7 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         own rollout buffers, the whole call is ONE hipGraph replay -- sampling, gathers, forward, backward and Adam of every
         epoch (~100 launches each) -- plus one read-back of the logged scalars when a history is given."""
         if self.fused_learn:
-            self._learn_fused(rollout, rows)
+            (self._learn_fused_cnn if self.body == "cnn" else self._learn_fused)(rollout, rows)
             if history is not None:
                 self._log_stats(history)
             return history
