@@ -347,6 +347,23 @@ SGK_API int sgk_tabq_rollout(sgk_tabq *q, int64_t n_steps, int cheat);
 #define SGK_TABQ_KERNEL_LDS 1
 #define SGK_TABQ_KERNEL_HBM 2
 SGK_API int sgk_tabq_rollout_ex(sgk_tabq *q, int64_t n_steps, int cheat, int kernel);
+/* default_eval (reference common/eval.py:8-56) for every (env, agent) pair in ONE launch, from the envs' current states (a caller
+ * that restates eval.py:13 calls sgk_metrics_reset and sgk_reset first): n_reset_steps lockstep steps of {greedy act, env.step,
+ * reset of the envs that are over} -- eval.py:19-39 while t < eval_timesteps: TabularQAgent.act is np.argmax of the board's row
+ * (value.py:33-35, first maximum wins), a finished episode is booked (eval.py:22) and the env reset (eval.py:23) --, then
+ * n_tail_steps of {greedy act, env.step} WITHOUT reset, in which an env whose episode has ended idles as under sgk_step
+ * (eval.py:32-33: the loop leaves at the first `done` at or after eval_timesteps; max_iterations steps end every episode).
+ * Equal, bit for bit, to that many rounds of {sgk_tabq_act(explore = 0), sgk_step, sgk_reset_done} and {sgk_tabq_act(0), sgk_step}:
+ * state words, step records (an idle env's names the action its agent chose), episode arrays, metrics, reset counters, side
+ * state, the handle's step accounting; an env that is over on entry idles through the first step and is reset behind it. The
+ * boards are materialised once, at the end. The tables, the agent step counter and epsilon are not touched -- except that on a
+ * hashed level (tomato watering) act() claims a slot for a board it has not seen, as the reference's defaultdict inserts on a
+ * miss (value.py:31,34-35); a full table reads as zeros and raises the overflow flag (sgk_tabq_hash_info).
+ * kernel: as for sgk_tabq_rollout_ex -- LDS names the on-chip kernel (each agent's greedy policy folded into a 64-bit register
+ * word at entry, no table access per step; envs whose state is the agent cell only, SGK_ERR_INVALID otherwise), HBM the one that
+ * gathers a row per state change (any env), AUTO the on-chip kernel wherever it qualifies. Both counts 0: nothing happens.
+ * No allocation, no host synchronisation: capturable in a hipGraph. */
+SGK_API int sgk_tabq_eval(sgk_tabq *q, int64_t n_reset_steps, int64_t n_tail_steps, int kernel);
 /* The tables where they live: [n_states][n_envs][n_actions] float64, STATE-major (ABI 3) -- the row of state s of agent e starts at
  * ((s * n_envs) + e) * n_actions doubles: one lane = one agent, so a wave's 64 rows of a state are 2 KB contiguous (ABI 2 had
  * [n_envs][n_states][n_actions]: 64 separate lines per row access of a wave). sgk_tabq_copy_table hands out the agent-major

@@ -1533,6 +1533,35 @@ int sgk_tabq_rollout_ex(sgk_tabq *q, int64_t n_steps, int cheat, int kernel) try
 
 int sgk_tabq_rollout(sgk_tabq *q, int64_t n_steps, int cheat) try { return sgk_tabq_rollout_ex(q, n_steps, cheat, SGK_TABQ_KERNEL_AUTO); } SGK_CATCH_STATUS
 
+int sgk_tabq_eval(sgk_tabq *q, int64_t n_reset_steps, int64_t n_tail_steps, int kernel) try {
+  if (!q) return fail(SGK_ERR_INVALID, "handle is NULL");
+  sgk_env *h = q->env;
+  SGK_CHECK_HANDLE(h);
+  if (n_reset_steps < 0) return fail(SGK_ERR_INVALID, "n_reset_steps < 0");
+  if (n_tail_steps < 0) return fail(SGK_ERR_INVALID, "n_tail_steps < 0");
+  if (kernel < SGK_TABQ_KERNEL_AUTO || kernel > SGK_TABQ_KERNEL_HBM) return fail(SGK_ERR_INVALID, "unknown kernel choice");
+  sgk::Shard &s = h->sh;
+  const size_t lds_need = sgk::tabq_rollout_lds_bytes(s);  // (the same levels qualify: table state = agent cell, <= 32 live slots)
+  const bool lds_possible = lds_need != 0 && lds_need <= 160u * 1024u;
+  if (kernel == SGK_TABQ_KERNEL_LDS && !lds_possible)
+    return fail(SGK_ERR_INVALID, "this env's tables do not fit LDS: the on-chip (policy-in-registers) kernel cannot run");
+  if (n_reset_steps > INT64_MAX - n_tail_steps) return fail(SGK_ERR_INVALID, "n_reset_steps + n_tail_steps overflows");
+  const int64_t n_steps = n_reset_steps + n_tail_steps;
+  if (n_steps == 0) return SGK_OK;
+  if (lds_possible && kernel != SGK_TABQ_KERNEL_HBM) {
+    SGK_HIP(sgk::launch_tabq_eval(s, q->tq, n_reset_steps, n_tail_steps, h->stream));
+  } else {
+    SGK_HIP(sgk::launch_tabq_eval_hbm(s, q->tq, n_reset_steps, n_tail_steps, h->stream));
+  }
+  SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
+  // greedy act() and env.step only: the agent step counter (and with it epsilon) stays where it is
+  q->rows_stale = true;  // the kernels keep no rows: the per-step kernels' slots are re-tagged before their next use
+  s.lockstep_t += (uint64_t)n_steps;
+  h->t_dev_stale = true;
+  h->steps_issued += s.n * n_steps;
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_tabq_table_dev(sgk_tabq *q, double **table_dev, int64_t *n_states, int64_t *n_actions) try {
   if (!q) return fail(SGK_ERR_INVALID, "handle is NULL");
   q->rows_stale = true;  // the caller may write through the pointer: the per-step kernels re-read the table afterwards

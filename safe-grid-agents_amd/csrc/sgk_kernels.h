@@ -196,6 +196,10 @@ hipError_t launch_tabq_step(const Shard &sh, const TabqShard &tq, int cheat, uin
 hipError_t launch_tabq_rollout(const Shard &sh, const TabqShard &tq, int64_t n_steps, int cheat, hipStream_t st);
 hipError_t launch_tabq_rollout_hbm(const Shard &sh, const TabqShard &tq, int64_t n_steps, int cheat, hipStream_t st);
 size_t tabq_rollout_lds_bytes(const Shard &sh);
+// default_eval (eval.py:8-56) in one launch: n_reset_steps of {greedy act, env.step, reset of the finished envs}, then n_tail_steps
+// without the reset. launch_tabq_eval: the policy-in-registers kernel, for the shards tabq_rollout_lds_bytes() != 0 qualifies
+hipError_t launch_tabq_eval(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st);
+hipError_t launch_tabq_eval_hbm(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st);
 
 int host_random_action(uint64_t seed, uint64_t env, uint64_t t);  // sgk_host_debug.cpp
 int host_debug_transition(const SgkRules &R, int agent_cell, int box_cell, int action, int out[5]);

@@ -863,6 +863,226 @@ __global__ __launch_bounds__(WG) void tabq_rollout_hbm_kernel(TabqArgs a, int64_
   acc_flush(acc, a.metrics);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Fused greedy evaluation: default_eval (reference eval.py:8-56) for N private agents in ONE launch -- n_reset_steps lockstep
+// steps of {act, env.step, reset of the finished envs}, then n_tail_steps of {act, env.step} in which an env whose episode has
+// ended idles, as under sgk_step. What it replaces is that many rounds of {sgk_tabq_act(explore = 0), sgk_step, sgk_reset_done}
+// issued from the host, and it leaves what they leave: state words, step records (an idle env's names the action its agent chose),
+// episode arrays, metrics, aux, reset counters, the pending-action half of the row tags. The tables, the agent step counter and
+// epsilon are not touched: the greedy policy is a constant of the launch.
+//
+// Policy in registers (the levels whose table state is the agent's cell, <= 32 live slots): one lane = one agent. At entry the lane
+// reads its agent's live rows once (the rollout kernel's 2 KB-contiguous state-major loads) and keeps argmax4 of each as two bits
+// of a 64-bit policy word. A step is then: action = (policy >> 2 * slot) & 3, the slot-indexed transition entry through the
+// crossbar (T0 / T1 as in tabq_rollout_kernel), frame / ret / hid bookkeeping. No LDS memory, no table access, so the kernel is
+// sized for occupancy: nothing per wave but ~40 registers. "Over" is a per-lane run-time flag here (the tail does not reset);
+// EVERY lane keeps executing the ds_bpermute -- an over or out-of-batch lane looks up slot 0 for a phantom agent and drops the
+// answer -- because any lane may hold the table entry another lane needs.
+// ------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(64) void tabq_eval_kernel(TabqArgs a, int64_t n_reset_steps, int64_t n_tail_steps) {
+  constexpr int AG = 64;
+  const SgkRules *__restrict__ Rg = a.rules;  // wave-uniform fields: scalar loads, once
+  const int lane = threadIdx.x;
+  const int n_live = Rg->n_live_slots, max_it = Rg->max_iterations;
+  const int start_cell = Rg->start_agent, start_slot = Rg->state_slot[Rg->start_agent];
+  const int start_box = Rg->start_box, start_ext = Rg->start_ext;
+  uint32_t T0 = 0, T1 = 0;
+  {
+    const int n_ent = n_live * 4;
+    auto entry = [&](int i) -> uint32_t { return i < n_ent ? Rg->trans[(int)Rg->slot_cell[i >> 2] * 4 + (i & 3)] : 0u; };
+    T0 = entry(lane);
+    if (NT > 1) T1 = entry(lane + 64);
+  }
+  const int my_cell = Rg->slot_cell[lane];  // lane r < n_live: the cell of row r
+  const int64_t n_groups = (a.n + AG - 1) / AG;
+  EpisodeAcc acc;
+  acc_init(acc);
+  for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+    const int64_t env0 = g * AG;
+    const int64_t env = env0 + lane;
+    const bool valid = env < a.n;
+    const int64_t env_src = valid ? env : env0;  // (a lane past the batch's end reads its group's first agent and writes nothing)
+    // the greedy policy: argmax4 of every live row, two bits per slot (np.argmax: first maximum wins)
+    uint64_t policy = 0;
+    for (int r = 0; r < n_live; ++r) {
+      const int cell = __builtin_amdgcn_readlane(my_cell, r);
+      const double *src = a.table + row_of(a.n, cell, env_src);  // the wave's 64 rows of this state: 2 KB contiguous
+      const double2 v01 = reinterpret_cast<const double2 *>(src)[0], v23 = reinterpret_cast<const double2 *>(src)[1];
+      policy |= (uint64_t)argmax4(v01.x, v01.y, v23.x, v23.y) << (2 * r);
+    }
+    EnvState s = initial_state(*Rg);
+    if (valid) s = unpack_state(a.state[env]);
+    bool over = !valid || s.over != 0;
+    int pos = s.pos, frame = s.frame, ret = s.ret, hid = s.hid;
+    int si = over ? 0 : (int)Rg->state_slot[pos];  // 0 while the lane has no live env
+    if (si >= n_live) si = 0;  // (cannot happen for a live env: it stands on a non-terminal cell)
+    bool reset_seen = false;
+    // the last step, for the record and the row tag: its table entry and action, the cell the action was chosen on, whether the
+    // env idled through it and whether it ended an episode
+    uint32_t e_last = 0;
+    int action_last = 0, cell_last = 0;
+    bool idle_last = true, fin_last = false;
+
+    auto step = [&](const bool reset_phase) {
+      const int action = (int)((uint32_t)(policy >> (2 * si)) & 3u);
+      const int idx = si * 4 + action;
+      uint32_t e = (uint32_t)__builtin_amdgcn_ds_bpermute(idx << 2, (int)T0);
+      if (NT > 1) {
+        const uint32_t e1 = (uint32_t)__builtin_amdgcn_ds_bpermute(idx << 2, (int)T1);
+        e = (idx & 64) ? e1 : e;
+      }
+      const bool live = !over;
+      const bool term = (e & 0x1000000u) != 0;
+      cell_last = pos;
+      idle_last = !live;
+      e_last = e;
+      action_last = action;
+      frame += live ? 1 : 0;
+      ret += live ? (int)(int8_t)(e >> 8) : 0;
+      hid += live ? (int)(int8_t)(e >> 16) : 0;
+      pos = live ? (int)(e & 0xffu) : pos;
+      si = (live && !term) ? (int)(e >> 25) : 0;
+      const bool finished = live && (term || frame >= max_it);
+      fin_last = finished;
+      if (finished) {
+        acc_add(acc, true, ret, hid);
+        a.last_return[env] = ret;
+        a.last_perf[env] = hid;
+        bump_episode_count(a.n_episodes, env);
+        over = true;
+        si = 0;
+      }
+      if (reset_phase && valid && over) {  // sgk_reset_done: every env that is over, the ones that came in over included
+        frame = 0;
+        ret = 0;
+        hid = 0;
+        pos = start_cell;
+        si = start_slot;
+        over = false;
+        reset_seen = true;
+      }
+    };
+    for (int64_t k = 0; k < n_reset_steps; ++k) step(true);
+    for (int64_t k = 0; k < n_tail_steps; ++k) step(false);
+
+    if (valid) {
+      s.pos = pos;
+      s.frame = frame;
+      s.ret = ret;
+      s.hid = hid;
+      s.over = over ? 1 : 0;
+      if (reset_seen) {
+        s.box = start_box;
+        s.mode = 0;
+        s.ext = start_ext;
+      }
+      a.state[env] = pack_state(s);
+      uint32_t rec;
+      if (!idle_last) {
+        rec = pack_rec((int)(int8_t)(e_last >> 8), (int)(int8_t)(e_last >> 16), fin_last ? 1 : 0, action_last);
+      } else {
+        // the env idled through the last step: its record names the action its agent chose on the cell it stood on (sgk_tabq_act
+        // looks every env's board up) -- a terminal cell or, after a time-out, a live one: the row in HBM serves both
+        const double2 r01 = reinterpret_cast<const double2 *>(a.table + row_of(a.n, cell_last, env))[0];
+        const double2 r23 = reinterpret_cast<const double2 *>(a.table + row_of(a.n, cell_last, env))[1];
+        rec = pack_rec(0, 0, 1, argmax4(r01.x, r01.y, r23.x, r23.y));
+      }
+      a.rec[env] = rec;
+      a.tags[env] = (uint64_t)(idle_last ? 0xffffffffu : (uint32_t)cell_last) | 0xffffffff00000000ull;  // the last act() is pending; no row kept
+    }
+  }
+  acc_flush(acc, a.metrics);
+}
+
+// The same evaluation for every other level (and any level when asked for): tabq_rollout_hbm_kernel without the draw, the update
+// and the table store. One lane = one agent for the whole launch, state word, side state and episode index in registers; per step
+// one state_index + 32-byte row gather, skipped while the env's state does not change (an idle env) or its state index stays (a
+// refused move). On the hashed level the lookup is what claims a slot, as greedy act() does in the reference (value.py:34-36: a
+// defaultdict inserts on a miss): boards are looked up in the order sgk_tabq_act would -- the current board of every env at the
+// top of every step, an over env's included -- and looking a board up again changes nothing, so skipping the repeat is exact.
+template <int ENV>
+__global__ __launch_bounds__(WG) void tabq_eval_hbm_kernel(TabqArgs a, int64_t n_reset_steps, int64_t n_tail_steps) {
+  __shared__ SgkRules R;
+  stage_rules(R, a.rules);
+  EpisodeAcc acc;
+  acc_init(acc);
+  const int64_t n_steps = n_reset_steps + n_tail_steps;
+  const int64_t n_tiles = (a.n + WG - 1) / WG;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t env = tile * WG + threadIdx.x;
+    const bool valid = env < a.n;
+    EnvState s = initial_state(R);
+    if (valid) s = unpack_state(a.state[env]);
+    load_episode_index<ENV>(s, a.n_resets, env, valid);
+    const uint64_t ge = a.env_base + (uint64_t)env;
+    AuxRegs ax;  // the env's float64 side state, in registers for the whole launch (friend or foe; dead code elsewhere)
+    ax.init();
+    if (HasAux<ENV>::value && valid) ax.load(a.aux + env * SGK_AUX_DOUBLES);
+    int si = -2;           // the state index whose row is in hand (-1: a full hash table has no row for the board -- zeros; -2: none yet)
+    bool changed = valid;  // the state word changed since the last lookup
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+    uint32_t rec = 0, tag_lo = 0xffffffffu;
+    for (int64_t k = 0; k < n_steps; ++k) {
+      // ---- act (value.py:33-35) on the board the env shows, whether its episode is over or not ----
+      if (changed) {
+        const int sn = state_index<ENV>(R, s, a, env);
+        if (sn != si) {
+          q0 = q1 = q2 = q3 = 0.0;
+          if (sn >= 0) {
+            const double2 *rp = reinterpret_cast<const double2 *>(a.table + row_of(a.n, sn, env));
+            const double2 a01 = rp[0], a23 = rp[1];
+            q0 = a01.x; q1 = a01.y; q2 = a23.x; q3 = a23.y;
+          }
+          si = sn;
+        }
+        changed = false;
+      }
+      const int action = argmax4(q0, q1, q2, q3);
+      tag_lo = (s.over || si < 0) ? 0xffffffffu : (uint32_t)si;
+      // ---- env.step ----
+      bool finished = false;
+      int r_obs = 0, r_hid = 0, executed = action;
+      if (valid && !s.over) {
+        int term;
+        executed = env_actual_action<ENV>(R, s, a.seed, ge, action);  // what the env executes (whisky)
+        if (HasAux<ENV>::value) transition_with<ENV>(R, s, executed, r_obs, r_hid, term, ax);
+        else transition<ENV>(R, s, executed, r_obs, r_hid, term);
+        s.frame += 1;
+        s.ret += r_obs;
+        s.hid += r_hid;
+        finished = term || s.frame >= R.max_iterations;
+        changed = true;
+      }
+      rec = pack_rec(r_obs, r_hid, (valid && (s.over || finished)) ? 1 : 0, executed);
+      acc_add(acc, finished, s.ret, s.hid);
+      if (finished) {
+        a.last_return[env] = s.ret;
+        a.last_perf[env] = s.hid;
+        bump_episode_count(a.n_episodes, env);
+        s.over = 1;
+      }
+      // ---- sgk_reset_done, first phase only: every env that is over, the ones that came in over included ----
+      if (k < n_reset_steps && valid && s.over) {
+        const int epi = s.epi + 1;  // this reset's index; n_resets[env] is brought up to date once, after the loop
+        s = initial_state(R);
+        s.epi = epi;
+        if (HasAux<ENV>::value) begin_episode_with<ENV>(R, s, a.seed, ge, ax);
+        else begin_episode<ENV>(R, s, a.seed, ge);
+        changed = true;
+      }
+    }
+    if (valid) {
+      a.state[env] = pack_state(s);
+      a.rec[env] = rec;  // boards are re-materialised by the caller (launch_reset mode 2)
+      a.tags[env] = (uint64_t)tag_lo | 0xffffffff00000000ull;  // the last act() is pending; no row kept
+      if (HasEnvDraws<ENV>::value) a.n_resets[env] = s.epi;
+      if (HasAux<ENV>::value && ax.dirty) ax.store(a.aux + env * SGK_AUX_DOUBLES);
+    }
+  }
+  acc_flush(acc, a.metrics);
+}
+
 // hashed levels: slots in use in the fullest agent's table (one lane per agent; a diagnostic, not a hot path)
 __global__ __launch_bounds__(WG) void tabq_hash_used_kernel(const uint32_t *__restrict__ keys, int64_t n, int cap, int32_t *__restrict__ max_used) {
   for (int64_t env = (int64_t)blockIdx.x * WG + threadIdx.x; env < n; env += (int64_t)gridDim.x * WG) {
@@ -1003,6 +1223,25 @@ hipError_t launch_tabq_rollout(const Shard &sh, const TabqShard &tq, int64_t n_s
     a.t_agent += chunk;
   }
   return err;
+}
+
+// The policy-in-registers evaluation holds no LDS, so its grid is sized for occupancy alone: one wave per workgroup, up to 32
+// resident waves per CU (8 per SIMD -- the wave's ~40 registers allow it), more groups than that walked in a grid-stride loop.
+hipError_t launch_tabq_eval(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st) {
+  (void)hipGetLastError();  // drop a stale error another HIP user of this thread may have left
+  TabqArgs a = make_tabq_args(sh, tq, 0);
+  const int grid = grid_for((sh.n + 63) / 64, sh.n_cus * 32);
+  if (sh.rules_host.n_live_slots * 4 <= 64) tabq_eval_kernel<1><<<dim3(grid), dim3(64), 0, st>>>(a, n_reset_steps, n_tail_steps);
+  else tabq_eval_kernel<2><<<dim3(grid), dim3(64), 0, st>>>(a, n_reset_steps, n_tail_steps);
+  return hipGetLastError();
+}
+
+hipError_t launch_tabq_eval_hbm(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st) {
+  (void)hipGetLastError();
+  TabqArgs a = make_tabq_args(sh, tq, 0);
+  int grid = grid_for((sh.n + WG - 1) / WG, sh.max_grid);
+  SGK_DISPATCH_ENV(sh.env_id, tabq_eval_hbm_kernel<E><<<dim3(grid), dim3(WG), 0, st>>>(a, n_reset_steps, n_tail_steps));
+  return hipGetLastError();
 }
 
 }  // namespace sgk

@@ -192,6 +192,7 @@ _SIGNATURES = {
     "sgk_tabq_step": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_uint32, _V]),
     "sgk_tabq_rollout": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int]),
     "sgk_tabq_rollout_ex": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "sgk_tabq_eval": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "sgk_tabq_table_dev": (ctypes.c_int, [_V, ctypes.POINTER(_V), ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int64)]),
     "sgk_tabq_invalidate_rows": (ctypes.c_int, [_V]),

@@ -237,6 +237,8 @@ class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
     parity with the CPU restatement is stated on that stream, not on numpy's Mersenne Twister.
     """
 
+    fused_eval = True  # loops.batched_default_eval hands the evaluation to evaluate(); False: its loop of per-step calls (A/B)
+
     def __init__(self, env, args):
         import torch
 
@@ -329,6 +331,29 @@ class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
         self.env._follow()
         self.env._version += 1
         _lib.check(self.lib.sgk_tabq_rollout_ex(self._h, int(n_steps), int(cheat), k))
+
+    def evaluate_enqueue(self, eval_timesteps, kernel="auto"):
+        """evaluate() without reading the metrics back: metrics_reset, reset and ONE sgk_tabq_eval launch, nothing that waits for
+        the GPU (the sequence can be recorded in a torch.cuda.graph; env.metrics() afterwards reads the result)."""
+        k = {"auto": _lib.TABQ_KERNEL_AUTO, "lds": _lib.TABQ_KERNEL_LDS, "hbm": _lib.TABQ_KERNEL_HBM}[kernel]
+        env = self.env
+        env.metrics_reset()
+        env.reset()
+        env._follow()
+        env._version += 1
+        _lib.check(self.lib.sgk_tabq_eval(self._h, max(int(eval_timesteps) - 1, 0), int(env.info.max_iterations), k))
+        env._sync_lib_to_torch()
+
+    def evaluate(self, eval_timesteps, kernel="auto"):
+        """default_eval (reference eval.py:8-56) for every (env, agent) pair, greedy, in ONE launch (sgk_tabq_eval): `eval_timesteps
+        - 1` lockstep steps with reset-on-done, then `max_iterations` steps without reset in which finished envs idle -- what
+        loops.batched_default_eval's loop of {act, env.step, reset_done} calls computes, bit for bit, tables and t untouched.
+        `kernel`: "auto", or "lds" / "hbm" to name the kernel (policy in registers / a row gather per state change; same
+        results). Returns BatchMetrics of the evaluation (the env's metrics are reset first)."""
+        from .metering import BatchMetrics
+
+        self.evaluate_enqueue(eval_timesteps, kernel)
+        return BatchMetrics(self.env.metrics(), self.env.reward_scale)
 
     def table(self):
         """The Q tables where they live: a float64 torch view [N, n_states, 4] over HBM (zero copy, sgk_tabq_table_dev). The memory

@@ -175,7 +175,13 @@ def batched_default_eval(agent, env, eval_timesteps):
     `eval_timesteps`, and leaves its loop at the first `done` at or after it (eval.py:19-39): whole episodes only.
     Lockstep form: `eval_timesteps - 1` iterations of {step, reset finished envs}, then steps WITHOUT reset until every
     env's current episode has ended (at most `max_iterations` more; finished envs idle, their steps are no-ops).
-    No host synchronisation inside the loop. Returns BatchMetrics of the evaluation (metrics are reset first)."""
+    No host synchronisation inside the loop. Returns BatchMetrics of the evaluation (metrics are reset first).
+
+    An agent with `fused_eval = True` and an `evaluate(eval_timesteps)` method (BatchedTabularQAgent: sgk_tabq_eval, the two
+    phases in ONE launch) is handed the whole evaluation; with `fused_eval = False` it goes through the loop of calls below.
+    The results are the same, bit for bit."""
+    if getattr(agent, "fused_eval", False) and hasattr(agent, "evaluate"):  # the whole evaluation is one launch (sgk_tabq_eval)
+        return agent.evaluate(eval_timesteps)
     boards = bool(getattr(agent, "reads_boards", False))  # table agents act on the state word; networks need the cells
     env.metrics_reset()
     env.reset()
