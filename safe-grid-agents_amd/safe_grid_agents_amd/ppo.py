@@ -541,7 +541,9 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         return keep
 
     def _cnn_learner(self, rollout, rows=None, rows_out=None):
-        """The filled _lib.SgkPpoCnnLearner of one _learn_fused_cnn call, and the flat rows tensor it points to (keep it alive)."""
+        """The filled _lib.SgkPpoCnnLearner of one _learn_fused_cnn call, and the flat rows tensor it points to (keep it alive).
+        Launches nothing; the first call allocates self._pl (Adam's state, the step counter, the workspace), which
+        tests/test_gpu_ppo_cnn_gradients.py relies on to set that state before the first epoch."""
         from . import _lib
         import ctypes
 

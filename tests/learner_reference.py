@@ -1,6 +1,6 @@
-"""Float64 references for the two fused MLP learners (sgk_dqn_sgd_step, sgk_ppo_epochs), on the CPU, and the seeded inputs that
-tests/test_learner_reference_cpu.py and tests/test_gpu_learner_gradients.py share. Plain torch on .double() tensors with autograd (or on
-.float() ones: the float32 yardstick); nothing here calls the product's learner code.
+"""Float64 references for the fused learners (sgk_dqn_sgd_step, sgk_ppo_epochs, sgk_ppo_cnn_epochs), on the CPU, and the seeded inputs
+that tests/test_learner_reference_cpu.py, tests/test_gpu_learner_gradients.py and tests/test_gpu_ppo_cnn_gradients.py share. Plain
+torch on .double() tensors with autograd (or on .float() ones: the float32 yardstick); nothing here calls the product's learner code.
 
   dqn_step64    DeepQAgent.learn's loss and gradients (value.py:113-136): target y = discount * max target_Q(s') * (1 - terminal) +
                 float32(reward * reward_scale), mse_loss over the [B,1]-vs-[B] broadcast (the default) or per sample, the gradients of
@@ -8,6 +8,8 @@ tests/test_learner_reference_cpu.py and tests/test_gpu_learner_gradients.py shar
   ppo_epoch64   one epoch of PPOBaseAgent (ppo.py's surrogate_loss): minibatch-normalised advantages (unbiased std), the ratio against
                 the old policy clipped to 1 +- clipping, critic_coeff x the critic's MSE, entropy_bonus x the entropy; the three logged
                 scalars and the gradients of the eight tensors.
+  ppo_cnn_epoch64  the same epoch for PPOCNNAgent's body (ppo.py: conv3x3 1 -> C, conv3x3 C -> C, the 1x1 bottleneck on the board added to
+                the trunk, conv3x3 + linear actor and critic heads): the three scalars, the gradients of the 14 tensors, the ratios.
   adam64        one element-wise Adam step with torch's formulas (the comment above adam_scalar in csrc/sgk_learn.hip), amsgrad when
                 a vmax is given. lr, beta1, beta2 and eps are taken as the float32 values the kernels receive; 1 - beta is then exact
                 in float32 (Sterbenz), so (1 - beta1) here is the kernel's own factor.
@@ -294,3 +296,231 @@ def inject_adam_state(g_c, seed, amsgrad):
         vs.append(v)
         xs.append((v * np.where(half, np.float32(0.5), np.float32(2.0))).astype(np.float32))
     return (ms, vs, xs) if amsgrad else (ms, vs, None)
+
+
+# ---- the conv body: sgk_ppo_cnn_epochs (csrc/sgk_ppo_cnn.hip) ------------------------------------------------------------------------
+# one level per board shape the kernels are instantiated for (height, width); x CNN_CHANNELS = the 21 instantiations
+CNN_SHAPES = collections.OrderedDict([
+    ("BoatRace-v0", (5, 5)), ("FriendFoe-v0", (6, 5)), ("SideEffectsSokoban-v0", (6, 6)), ("IslandNavigation-v0", (6, 8)),
+    ("ConveyorBelt-v0", (7, 7)), ("SafeInterruptibility-v0", (7, 8)), ("DistributionalShift-v0", (7, 9))])
+CNN_CHANNELS = (4, 5, 8)
+CNN_T, CNN_N = 3, 37              # the synthetic rollout: a short horizon and an odd number of trajectories
+# PPOCNNAgent's parameters in registration order (BatchedPPOAgent.CNN_PARAMS): conv1, conv2, the 1x1 bottleneck, the actor's conv and
+# linear layer, the critic's conv and linear layer; the old policy's ten actor-path tensors are the first ten
+CNN_TENSORS = ("w1", "b1", "w2", "b2", "wb", "bb", "wa", "ba", "la", "lab", "wv", "bv", "lv", "lvb")
+CNN_DEFAULT_HYPER = dict(lr=1e-3, clipping=0.2, critic_coeff=1.0, entropy_bonus=0.01)  # the agent's defaults (variant "defaults")
+# The current network = the old one + CNN_PERTURB x (the tensor's initialisation bound) x N(0, 1), element by element. With 0.25 the
+# log-ratios of the 111 rollout rows have a standard deviation of 0.11 to 0.48 over the cases and the ratios lie in 0.27 .. 2.2: at
+# least two rows above 1 + clipping, two below 1 - clipping and one inside for both clippings (0.1, 0.2), which ppo_cnn_inputs asserts,
+# and 31 to 57 of a minibatch's 64 rows outside the range (27 and 28 of 37 in the two batch-37 cases, 1 of 2 at batch 2).
+CNN_PERTURB = 0.25
+RATIO_MARGIN, ADV_MARGIN = 1e-3, 1e-2  # how far the branch rows stay from the clip bounds / from a zero advantage
+
+# variant: "clip" = PPO_HYPER, current network perturbed; "defaults" = the same under CNN_DEFAULT_HYPER; "tie" = old == current
+PpoCnnCase = collections.namedtuple("PpoCnnCase", "env channels batch seed variant")
+
+
+def _ppo_cnn_cases():
+    out = []
+
+    def add(env, channels, batch, variant="clip"):
+        out.append(PpoCnnCase(env + "-v0", channels, batch, 3000 + len(out), variant))
+
+    for env in CNN_SHAPES:
+        for channels in CNN_CHANNELS:
+            add(env[:-3], channels, 64)
+    add("SideEffectsSokoban", 8, 2)
+    add("SafeInterruptibility", 5, 2)
+    add("FriendFoe", 5, 37)
+    add("DistributionalShift", 8, 37, "defaults")
+    add("IslandNavigation", 4, 64, "tie")
+    reseed = CNN_RESEED
+    return [c._replace(seed=reseed.get((c.env, c.channels, c.batch, c.variant), c.seed)) for c in out]
+
+
+# seeds replaced because torch-float32's own error on one quantity was above 1e-5 / 8 with the first draw (the measured 8 err_t in
+# the comment); tests/test_learner_reference_cpu.py asks for inputs below it
+CNN_RESEED = {
+    ("SideEffectsSokoban-v0", 4, 64, "clip"): 3220,    # policy_loss 1.3e-05
+    ("SideEffectsSokoban-v0", 8, 64, "clip"): 3260,    # policy_loss 1.7e-05
+    ("ConveyorBelt-v0", 4, 64, "clip"): 3340,          # policy_loss 9.4e-05
+    ("SafeInterruptibility-v0", 5, 64, "clip"): 3423,  # bb 1.0e-05
+    ("SideEffectsSokoban-v0", 8, 2, "clip"): 3521,     # policy_loss 1.0e-05
+    ("SafeInterruptibility-v0", 5, 2, "clip"): 3541,   # policy_loss 1.1e-04
+    ("FriendFoe-v0", 5, 37, "clip"): 3560,             # lvb 3.3e-05
+}
+PPO_CNN_CASES = _ppo_cnn_cases()
+# the cases of the epoch-plumbing and ragged-rollout tests: one with C = 5 and one with C = 8, both under a full minibatch of 37
+PLUMBING_CASES = [c for c in PPO_CNN_CASES if c.batch == 37]
+
+
+def cnn_case_id(c):
+    return "%s-c%d-b%d%s" % (c.env[:-3], c.channels, c.batch, "" if c.variant == "clip" else "-" + c.variant)
+
+
+def ppo_cnn_hyper(case):
+    return dict(CNN_DEFAULT_HYPER if case.variant == "defaults" else PPO_HYPER)
+
+
+def _loss_kw(hyper):
+    return {k: hyper[k] for k in ("clipping", "critic_coeff", "entropy_bonus")}
+
+
+def _cnn_init(rng, channels, cells):
+    """torch's default Conv2d / Linear initialisation for PPOCNNAgent's 14 tensors (weights U(-k, k), k = 1 / sqrt(fan_in)), the biases
+    from U(-0.3, 0.3) instead (a dropped bias must show), and k per tensor."""
+    C = channels
+    shapes = [(C, 1, 3, 3), (C, C, 3, 3), (C, 1, 1, 1), (C, C, 3, 3), (4, C * cells), (C, C, 3, 3), (1, C * cells)]
+    params, bounds = [], []
+    for shape in shapes:
+        k = 1.0 / np.sqrt(float(np.prod(shape[1:])))
+        params += [rng.uniform(-k, k, shape).astype(np.float32), rng.uniform(-0.3, 0.3, shape[:1]).astype(np.float32)]
+        bounds += [k, 0.3]
+    return params, bounds
+
+
+def ppo_cnn_gather(d, rows):
+    """Boards [B, H, W], actions and returns of the flat rollout rows t * N + trajectory."""
+    rows = np.asarray(rows)
+    t, n = rows // CNN_N, rows % CNN_N
+    return d["states"][t, n].reshape((len(rows),) + d["shape"]), d["actions"][t, n], d["returns"][n, t]
+
+
+def ppo_cnn_epoch64(params, old_params, boards, actions, returns, clipping, critic_coeff, entropy_bonus, dtype=torch.float64):
+    """One epoch of PPOCNNAgent (ppo.py: PPOCNNAgent.forward + PPOBaseAgent.surrogate_loss) on a minibatch of boards [B, H, W]: the three
+    logged scalars, the gradients of the 14 tensors in CNN_TENSORS order, the ratios and the critic's values."""
+    F = torch.nn.functional
+    T = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).to(dtype)  # noqa: E731
+    p = [T(x).requires_grad_(True) for x in params]
+    o = [T(x) for x in old_params]
+    x, r = T(boards).unsqueeze(1), T(returns)
+    a = torch.as_tensor(np.asarray(actions, dtype=np.int64)).unsqueeze(1)
+
+    def trunk(w):
+        h = torch.relu(F.conv2d(x, w[0], w[1], padding=1))
+        return torch.relu(F.conv2d(h, w[2], w[3], padding=1)) + F.conv2d(x, w[4], w[5])
+
+    def head(t, wc, bc, wl, bl):
+        return torch.relu(F.conv2d(t, wc, bc, padding=1)).flatten(1) @ wl.t() + bl
+
+    tr = trunk(p)
+    logp_all = torch.log_softmax(head(tr, *p[6:10]), dim=-1)
+    values = head(tr, *p[10:14]).reshape(-1)
+    advantage = r - values
+    advantage = (advantage - advantage.mean()) / advantage.std()
+    with torch.no_grad():
+        old_logp = torch.log_softmax(head(trunk(o), *o[6:10]), dim=-1).gather(1, a).squeeze(1)
+    ratio = torch.exp(logp_all.gather(1, a).squeeze(1) - old_logp)
+    entropy = -(logp_all.exp() * logp_all).sum(-1).mean()
+    value_loss = ((values - r) ** 2).mean()
+    policy_loss = -torch.min(advantage * ratio, advantage * ratio.clamp(1 - clipping, 1 + clipping)).mean()
+    loss = policy_loss + critic_coeff * value_loss - entropy_bonus * entropy
+    grads = torch.autograd.grad(loss, p)
+    return {"stats": [float(policy_loss.detach()), float(value_loss.detach()), float(entropy.detach())], "grads": [g.double().numpy() for g in grads],
+            "ratio": ratio.detach().double().numpy(), "values": values.detach().double().numpy(),
+            "advantage": advantage.detach().double().numpy()}
+
+
+def ppo_cnn_row_conditions(case, d):
+    """What the minibatch d["rows"] of a case holds, evaluated in float64: a dict of named booleans, all of which must be True."""
+    h = ppo_cnn_hyper(case)
+    lo, hi = 1 - h["clipping"], 1 + h["clipping"]
+    rows, n = d["rows"], CNN_T * CNN_N
+    r64 = ppo_cnn_epoch64(d["cur"], d["old"][:10], *ppo_cnn_gather(d, rows), **_loss_kw(h))
+    ratio, adv = r64["ratio"], r64["advantage"]
+    above, below = ratio >= hi + RATIO_MARGIN, ratio <= lo - RATIO_MARGIN
+    inside = (ratio >= lo + RATIO_MARGIN) & (ratio <= hi - RATIO_MARGIN)
+    pos, neg = adv >= ADV_MARGIN, adv <= -ADV_MARGIN
+    out = {"rows in the rollout": bool((rows >= 0).all() and (rows < n).all()), "batch": len(rows) == case.batch}
+    if case.variant == "tie":
+        out["old == current"] = all((a == b).all() for a, b in zip(d["cur"], d["old"])) and bool((ratio == 1.0).all())
+    elif case.batch == 2:
+        out["one row outside"] = bool((above | below)[0])
+        out["one row inside"] = bool(inside[1])
+        out["two different rows"] = rows[0] != rows[1] and not (ppo_cnn_gather(d, rows[:1])[0] == ppo_cnn_gather(d, rows[1:])[0]).all()
+    if case.batch >= 8:
+        if case.variant != "tie":
+            out["above, positive advantage"] = bool(above[0] and pos[0])
+            out["above, negative advantage"] = bool(above[1] and neg[1])
+            out["below, positive advantage"] = bool(below[2] and pos[2])
+            out["below, negative advantage"] = bool(below[3] and neg[3])
+            out["inside"] = bool(inside[4] and (pos | neg)[4])
+        out["last row"] = rows[5] == n - 1
+        out["row 0"] = rows[6] == 0
+        out["a duplicate"] = rows[7] == rows[1]
+    return out
+
+
+def ppo_cnn_inputs(case):
+    """The synthetic rollout [T = CNN_T, N = CNN_N] (boards of seeded integers 0..5 in every cell, the border ring included; every pair
+    valid), the old policy and the current network (float32, CNN_TENSORS order) and the minibatch rows t * N + trajectory. At batch >= 8
+    rows[0..7] are: ratio above 1 + clipping with a positive / a negative normalised advantage, below 1 - clipping with a positive / a
+    negative one, a ratio inside the range, the last row T * N - 1, row 0, and rows[1] again; the first four rows' returns are set to
+    the critic's value +- 4 for that sign. At batch 2: a row outside and a row inside. "tie": old == current (every ratio is 1).
+    Also "rows2" (a second minibatch, for the two-epoch test) and "ragged_lengths" (a seeded mix of 0..3 with a 0 in it)."""
+    rng = np.random.default_rng(case.seed)
+    (H, W), C, n = CNN_SHAPES[case.env], case.channels, CNN_T * CNN_N
+    h = ppo_cnn_hyper(case)
+    d = {"shape": (H, W), "states": rng.integers(0, 6, (CNN_T, CNN_N, H * W)).astype(np.int8),
+         "actions": rng.integers(0, 4, (CNN_T, CNN_N)).astype(np.uint8),
+         "returns": rng.uniform(-5.0, 5.0, (CNN_N, CNN_T)).astype(np.float32),
+         "lengths": np.full((CNN_N,), CNN_T, dtype=np.int32)}
+    old, bounds = _cnn_init(rng, C, H * W)
+    noise = [rng.standard_normal(p.shape).astype(np.float32) for p in old]
+    d["old"] = old
+    if case.variant == "tie":
+        d["cur"] = [p.copy() for p in old]
+    else:
+        d["cur"] = [(p + np.float32(CNN_PERTURB * k) * z).astype(np.float32) for p, k, z in zip(old, bounds, noise)]
+    rows = rng.integers(0, n, case.batch)
+    d["rows2"] = rng.integers(0, n, case.batch).astype(np.int64)
+    lengths = rng.integers(0, CNN_T + 1, CNN_N).astype(np.int32)
+    lengths[case.seed % CNN_N] = 0
+    d["ragged_lengths"] = lengths
+    assert 3 * int(lengths.sum()) >= n and set(lengths.tolist()) == {0, 1, 2, 3}
+    if case.variant != "tie":
+        full = ppo_cnn_epoch64(d["cur"], old[:10], *ppo_cnn_gather(d, np.arange(n))[:2], np.zeros(n), **_loss_kw(h))
+        ratio, values = full["ratio"], full["values"]  # (neither depends on the returns)
+        lo, hi = 1 - h["clipping"], 1 + h["clipping"]
+        above, below = np.flatnonzero(ratio >= hi + 5 * RATIO_MARGIN), np.flatnonzero(ratio <= lo - 5 * RATIO_MARGIN)
+        inside = np.flatnonzero((ratio >= lo + 5 * RATIO_MARGIN) & (ratio <= hi - 5 * RATIO_MARGIN))
+        assert len(above) >= 2 and len(below) >= 2 and len(inside) >= 1, (case, len(above), len(below), len(inside))
+        if case.batch == 2:
+            rows[:] = [(above if case.seed % 2 else below)[0], inside[0]]
+        else:
+            rows[:5] = [above[0], above[1], below[0], below[1], inside[0]]
+            for row, sign in zip(rows[:4], (4.0, -4.0, 4.0, -4.0)):
+                d["returns"][row % CNN_N, row // CNN_N] = np.float32(values[row] + sign)
+    if case.batch >= 8:
+        rows[5:8] = [n - 1, 0, rows[1]]
+    d["rows"] = rows.astype(np.int64)
+    bad = [k for k, ok in ppo_cnn_row_conditions(case, d).items() if not ok]
+    assert not bad, (case, bad)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def ppo_cnn_yardstick(case):
+    """(inputs, float64 reference, err_t per tensor and per scalar: the same function in float32) of a conv case; once per process."""
+    d = ppo_cnn_inputs(case)
+    args, kw = (d["cur"], d["old"][:10]) + ppo_cnn_gather(d, d["rows"]), _loss_kw(ppo_cnn_hyper(case))
+    r64, r32 = ppo_cnn_epoch64(*args, **kw), ppo_cnn_epoch64(*args, dtype=torch.float32, **kw)
+    err_t = {k: rel_err(a, b) for k, a, b in zip(CNN_TENSORS, r32["grads"], r64["grads"])}
+    for i, k in enumerate(("policy_loss", "value_loss", "entropy")):
+        err_t[k] = cnn_stat_err(case, r64, i, r32["stats"][i])
+    return d, r64, err_t
+
+
+def cnn_stat_pair(case, r64, i, got):
+    """(got', want') of logged scalar i (policy loss, value loss, entropy) such that rel_err(got', want') is the error to hold against
+    `bound`: the value and the float64 reference. With old == current ("tie") every ratio is 1 and the policy loss is
+    -mean(normalised advantage): identically 0 (1e-17 in float64), so an error relative to it means nothing; there the error is taken
+    relative to the mean |term| of that sum, mean |normalised advantage| (~0.8), the scale its roundings have."""
+    if case.variant == "tie" and i == 0:
+        scale = float(np.abs(r64["advantage"]).mean())
+        return float(got) - r64["stats"][0] + scale, scale
+    return float(got), r64["stats"][i]
+
+
+def cnn_stat_err(case, r64, i, got):
+    return rel_err(*cnn_stat_pair(case, r64, i, got))

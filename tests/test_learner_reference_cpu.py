@@ -1,7 +1,9 @@
 """tests/learner_reference.py checked on the CPU: (1) dqn_step64 + adam64 reproduce the reference's own DeepQAgent.learn run
 (tests/golden/deepq_learn.npz) -- the reference is the right formula; (2) the yardstick of tests/test_gpu_learner_gradients.py: for
 every case there, torch-float32 autograd on the same inputs lies within err_t of the float64 reference with 8 err_t <= 1e-5, so the cap
-of the GPU tests is never the binding bound; (3) the cases named "clipped" / "unclipped" are what they say."""
+of the GPU tests is never the binding bound; (3) the cases named "clipped" / "unclipped" are what they say; (4) the same for the conv
+body (ppo_cnn_epoch64 against PPOCNNAgent.surrogate_loss and the reference's own ppo-cnn run; the yardstick and the rows of every case
+of tests/test_gpu_ppo_cnn_gradients.py)."""
 import json
 import os
 
@@ -155,3 +157,115 @@ def test_rtol_on_the_first_moment_needs_the_operands_scale():
     scale = np.abs(m0.astype(np.float64)) + R.one_minus_beta1() * np.abs(g_c - m0)
     assert (np.abs(m1 - m_ref) / (1e-6 * np.abs(m_ref))).max() > 100.0
     assert (np.abs(m1 - m_ref) / (1e-6 * scale)).max() < 0.5
+
+
+# ---- the conv body (tests/test_gpu_ppo_cnn_gradients.py) -----------------------------------------------------------------------------
+def _cnn_agent(shape, channels, batch, hyper):
+    import types
+
+    import safe_grid_agents_amd as S
+
+    env = types.SimpleNamespace(action_space=types.SimpleNamespace(n=4), observation_space=types.SimpleNamespace(shape=(1,) + tuple(shape)))
+    args = types.SimpleNamespace(discount=0.99, batch_size=batch, rollouts=1, epochs=1, n_layers=2, n_channels=channels, device="cpu",
+                                 log_gradients=False, **hyper)
+    return S.PPOCNNAgent(env, args)
+
+
+@pytest.mark.parametrize("case", R.PLUMBING_CASES, ids=R.cnn_case_id)
+def test_ppo_cnn_epoch64_is_the_agents_surrogate_loss(case):
+    """ppo_cnn_epoch64 on float32 (the form the yardstick uses) against PPOCNNAgent.surrogate_loss + autograd on the CPU -- the
+    golden-pinned host implementation of ppo.py -- with the same weights and minibatch, for a C = 5 case under PPO_HYPER and the C = 8
+    case under the agent's defaults: the three scalars and the 14 gradients. Both are float32 torch on the same terms: 1e-5 of each
+    tensor's largest element."""
+    import torch
+
+    import safe_grid_agents_amd as S
+
+    d = R.ppo_cnn_inputs(case)
+    hyper = R.ppo_cnn_hyper(case)
+    agent = _cnn_agent(d["shape"], case.channels, case.batch, hyper)
+    own, old = dict(agent.named_parameters()), dict(agent.old_policy.named_parameters())
+    names = S.BatchedPPOAgent.CNN_PARAMS
+    assert len(names) == len(R.CNN_TENSORS) == 14
+    with torch.no_grad():
+        for k, cur, o in zip(names, d["cur"], d["old"]):
+            assert own[k].shape == cur.shape, k
+            own[k].copy_(torch.as_tensor(cur))
+            old[k].copy_(torch.as_tensor(o))
+    s, a, r = R.ppo_cnn_gather(d, d["rows"])
+    loss, pl, vl, en = agent.surrogate_loss(torch.as_tensor(s.astype(np.float32)).unsqueeze(1), torch.as_tensor(a.astype(np.int64)), torch.as_tensor(r))
+    grads = torch.autograd.grad(loss, [own[k] for k in names])
+    ref = R.ppo_cnn_epoch64(d["cur"], d["old"][:10], s, a, r, dtype=torch.float32, **{k: hyper[k] for k in ("clipping", "critic_coeff", "entropy_bonus")})
+    np.testing.assert_allclose(ref["stats"], [float(pl.detach()), float(vl.detach()), float(en.detach())], rtol=1e-5)
+    for k, g, want in zip(R.CNN_TENSORS, ref["grads"], grads):
+        assert g.shape == tuple(want.shape) and R.rel_err(g, want.numpy()) <= 1e-5, k
+
+
+def test_ppo_cnn_epoch64_reproduces_the_reference_ppo_cnn_runs_first_epochs(golden_dir):
+    """batched_ppo_cnn_boat.npz (the reference's PPOCNNAgent, 5 channels, batch 64): the weights before each iteration's learn, its
+    first epoch's rows (indices into the valid (t, env) pairs in that order), boards and returns through ppo_cnn_epoch64 in float64 give
+    the reference's recorded first-epoch policy loss, value loss and entropy, at the tolerance
+    test_fused_cnn_learner_reproduces_the_reference_ppo_cnn_run uses for them (rtol 2e-3 / atol 2e-5). The old policy is the current one
+    there (sync() before every gather): the recorded policy loss is -mean(normalised advantage) = 0 within float32 rounding."""
+    import batched_golden as BG
+    import safe_grid_agents_amd as S
+
+    fx = BG.PpoFixture("batched_ppo_cnn_boat.npz")
+    m = fx.meta
+    kw = {k: m[k] for k in ("clipping", "critic_coeff", "entropy_bonus")}
+    for it in range(fx.iterations):
+        w = fx.weights(it)
+        params = [w[k] for k in S.BatchedPPOAgent.CNN_PARAMS]
+        lengths, states, actions, returns = (fx.it(it, k) for k in ("lengths", "states", "actions", "returns"))  # [n], [n, horizon, ...]
+        valid = np.arange(fx.horizon)[:, None] < lengths[None, :]  # [T, n]
+        t_ix, n_ix = np.nonzero(valid)
+        pick = fx.it(it, "rows")[0]
+        t, n = t_ix[pick], n_ix[pick]
+        out = R.ppo_cnn_epoch64(params, params[:10], states[n, t].reshape(-1, 5, 5), actions[n, t], returns[n, t], **kw)
+        np.testing.assert_allclose(out["stats"], fx.losses(it)[0], rtol=2e-3, atol=2e-5)
+        assert (out["ratio"] == 1.0).all()
+
+
+@pytest.mark.parametrize("case", R.PPO_CNN_CASES, ids=R.cnn_case_id)
+def test_ppo_cnn_yardstick_and_rows(case):
+    """torch-float32's own error stays below the cap / 8 for every tensor and scalar of every conv case, and the minibatch holds the rows
+    it is meant to hold (learner_reference.ppo_cnn_row_conditions, in float64): the four clamp branches away from the clip bounds and
+    from a zero advantage, a row inside, the rollout's first and last row, a duplicate."""
+    d, r64, err_t = R.ppo_cnn_yardstick(case)
+    print("ppo-cnn %-40s " % R.cnn_case_id(case) + " ".join("%s %.2e" % kv for kv in err_t.items()))
+    assert set(err_t) == set(R.CNN_TENSORS) | {"policy_loss", "value_loss", "entropy"}
+    for k, e in err_t.items():
+        assert 8.0 * e <= R.CAP, (k, e)
+    conditions = R.ppo_cnn_row_conditions(case, d)
+    assert all(conditions.values()), conditions
+    want = {"tie": 6 if case.batch >= 8 else 3, "clip": 10 if case.batch >= 8 else 5, "defaults": 10}[case.variant]
+    assert len(conditions) == want, conditions  # (none of them silently left out)
+    h = R.ppo_cnn_hyper(case)
+    out = (r64["ratio"] < 1 - h["clipping"]) | (r64["ratio"] > 1 + h["clipping"])
+    assert (out.any() and not out.all()) or case.variant == "tie"
+    assert d["states"].shape == (R.CNN_T, R.CNN_N, d["shape"][0] * d["shape"][1]) and d["returns"].shape == (R.CNN_N, R.CNN_T)
+    ring = d["states"].reshape((-1,) + d["shape"])
+    border = np.concatenate([ring[:, 0].ravel(), ring[:, -1].ravel(), ring[:, :, 0].ravel(), ring[:, :, -1].ravel()])
+    assert set(border.tolist()) == set(range(6)) and (d["lengths"] == R.CNN_T).all()  # no constant wall ring
+    for g in r64["grads"]:
+        assert np.abs(g).max() > 0
+
+
+def test_conv_case_list_covers_what_the_issue_names():
+    from oracle import oracle as O
+
+    for env, shape in R.CNN_SHAPES.items():
+        assert tuple(O.shape(env)) == shape, env
+    cases = R.PPO_CNN_CASES
+    pairs = {(c.env, c.channels) for c in cases if c.batch == 64 and c.variant == "clip"}
+    assert pairs == {(e, ch) for e in R.CNN_SHAPES for ch in (4, 5, 8)} and len(pairs) == 21
+    assert len(set(R.CNN_SHAPES.values())) == 7
+    assert {c.batch for c in cases} == {2, 37, 64}
+    for batch in (2, 37):
+        small = [c for c in cases if c.batch == batch]
+        assert len({c.env for c in small}) == 2 and {c.channels for c in small} == {5, 8}
+    assert [c.batch for c in cases if c.variant == "defaults"] == [37] and sum(c.variant == "tie" for c in cases) == 1
+    assert R.ppo_cnn_hyper(next(c for c in cases if c.variant == "defaults")) == dict(lr=1e-3, clipping=0.2, critic_coeff=1.0, entropy_bonus=0.01)
+    assert all(R.ppo_cnn_hyper(c) == R.PPO_HYPER for c in cases if c.variant != "defaults")
+    assert len({c.seed for c in cases}) == len(cases) and not {c.seed for c in cases} & {c.seed for c in R.PPO_CASES + R.DQN_CASES}
+    assert {c.channels for c in R.PLUMBING_CASES} == {5, 8} and (R.CNN_T, R.CNN_N) == (3, 37)
