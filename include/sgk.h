@@ -549,6 +549,18 @@ typedef struct sgk_ppo_learner {
   double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
 } sgk_ppo_learner;
 SGK_API int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *learner);
+/* PPOBaseAgent.learn (reference policy_base.py:64-131) for n_members INDEPENDENT PPOMLPAgents in ONE launch, one workgroup per member:
+ * member m is the reference's run on the trajectories m * E .. (m + 1) * E - 1, E = n_trajectories / n_members (its `-r E`). Every
+ * tensor of `learner` but the rollout exists once per member, stacked on a leading member axis in one contiguous tensor, and the
+ * learner's pointers address member 0: w1 [n_members][H][n_cells], ..., m[i] / v[i] like their parameter, the old policy's tensors,
+ * step int64 [n_members], stats_out float [n_members][n_epochs][3], rows / rows_out int64 [n_members][n_epochs][batch]. The rollout is
+ * shared: n_trajectories = all members' trajectories (sgk_policy_rollout_members' outputs), rows are global (step * n_trajectories +
+ * trajectory) and member m draws its own from its own trajectories -- the trajectory from [0, E) by sgk_ppo_epochs' Philox call, then
+ * offset by m * E -- keyed by member_keys_dev[m] (uint64 [n_members], device) and its own Adam step; member_keys_dev NULL: the handle's
+ * seed for every member. All hyper-parameters are shared. n_members = 1 with member_keys_dev NULL IS sgk_ppo_epochs (the same kernel).
+ * SGK_ERR_INVALID for n_members < 1, n_trajectories % n_members != 0 and whatever sgk_ppo_epochs refuses. No allocation, no host
+ * synchronisation: can be recorded in a graph. A workgroup fills a CU's LDS: up to one member per CU runs at a time. */
+SGK_API int sgk_ppo_epochs_members(sgk_env *h, const sgk_ppo_learner *learner, int32_t n_members, const uint64_t *member_keys_dev);
 /* ---- PPOBaseAgent.learn (reference policy_base.py:64-131) for PPOCNNAgent (policy_cnn.py:17-81) on the device ------------ */
 /* All `n_epochs` minibatch updates of one learn() call, three launches per epoch enqueued by this one call (forward, backward, Adam;
  * no allocation, no host synchronisation, no float atomics: deterministic, and a captured replay equals the eager call bit for bit).
@@ -629,6 +641,19 @@ SGK_API int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t dra
 SGK_API int sgk_policy_rollout(sgk_env *h, const sgk_mlp_weights *w, int32_t mode, double epsilon, uint64_t draw_index0,
                                int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
                                sgk_step_rec *recs_out_dev);
+/* The same launch for n_members INDEPENDENT policies: the inner loop of PPOBaseAgent.gather_rollout (reference policy_base.py:133-177)
+ * of n_members agents at once. Member m acts in the envs m * E .. (m + 1) * E - 1, E = n_envs / n_members, with the m-th slice of
+ * weight tensors stacked on a leading member axis (w1t [n_members][n_cells][H], b1 [n_members][H], w2 [n_members][H][H], ...); `w`'s
+ * pointers address member 0. A workgroup serves one member for the whole launch. Env indices -- RNG keys (global env index),
+ * trajectory outputs [n_steps][n_envs][...], episode arrays -- are the handle's own, so member m's trajectories are those of a handle
+ * of E envs created at env_index_base + m * E running sgk_policy_rollout with member m's weights. member_metrics_dev: int64
+ * [n_members][SGK_METRICS_LEN] or NULL; each member's episodes are ALSO booked in its own vector (sums added, maxima raised: initialise
+ * the maxima to INT64_MIN as sgk_metrics_reset does), so the sums and counts over members are what the handle's vector gained and its
+ * maxima the maximum over members. n_members = 1 IS sgk_policy_rollout (the same kernel). SGK_ERR_INVALID for n_members < 1,
+ * n_envs % n_members != 0 and whatever sgk_policy_rollout refuses. */
+SGK_API int sgk_policy_rollout_members(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                                       uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev,
+                                       uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev);
 
 /* ---- PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186), batched ------------------------------ */
 /* rewards_dev / returns_dev: float32 [n_trajectories][t_max] row-major; lengths_dev: int32 [n_trajectories] or NULL

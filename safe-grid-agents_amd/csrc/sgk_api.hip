@@ -811,12 +811,18 @@ int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t draw_index,
   return SGK_OK;
 } SGK_CATCH_STATUS
 
-int sgk_policy_rollout(sgk_env *h, const sgk_mlp_weights *w, int32_t mode, double epsilon, uint64_t draw_index0, int32_t n_steps,
-                       uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev) try {
+// sgk_policy_rollout (one member) and sgk_policy_rollout_members: the same checks, the same kernel
+static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon, uint64_t draw_index0,
+                               int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
+                               sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) {
   SGK_CHECK_HANDLE(h);
   if (!w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3) return fail(SGK_ERR_INVALID, "NULL argument");
   if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
     return fail(SGK_ERR_INVALID, "sgk_policy_rollout is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)n_members);
+  if (h->sh.n % n_members != 0)
+    return fail(SGK_ERR_INVALID, "n_envs (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                (long long)h->sh.n, (int)n_members);
   if (mode != 0 && mode != 1) return fail(SGK_ERR_INVALID, "mode must be 0 (epsilon-greedy) or 1 (categorical)");
   if (n_steps < 0) return fail(SGK_ERR_INVALID, "n_steps < 0");
   if (flags & ~(uint32_t)(SGK_F_AUTO_RESET | SGK_F_MASK_FINISHED))
@@ -825,12 +831,24 @@ int sgk_policy_rollout(sgk_env *h, const sgk_mlp_weights *w, int32_t mode, doubl
   sgk::Shard &s = h->sh;
   sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
   SGK_HIP(sgk::launch_policy_rollout(s, mode, pw, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev,
-                                     reinterpret_cast<uint32_t *>(recs_out_dev), h->stream));
+                                     reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev));
   SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
   s.lockstep_t += (uint64_t)n_steps;
   h->t_dev_stale = true;
   h->steps_issued += s.n * n_steps;
   return SGK_OK;
+}
+
+int sgk_policy_rollout(sgk_env *h, const sgk_mlp_weights *w, int32_t mode, double epsilon, uint64_t draw_index0, int32_t n_steps,
+                       uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev) try {
+  return policy_rollout_impl(h, w, 1, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev, nullptr);
+} SGK_CATCH_STATUS
+
+int sgk_policy_rollout_members(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                               uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
+                               sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) try {
+  return policy_rollout_impl(h, w, n_members, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev,
+                             member_metrics_dev);
 } SGK_CATCH_STATUS
 
 int sgk_replay_store(sgk_env *h, int32_t phase, const uint8_t *actions_dev, int32_t cheat, int64_t slice, const int64_t *slice_dev,
@@ -1011,7 +1029,8 @@ int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *L, uint32_t 
   return dqn_sgd_step_impl(h, L, &rs);
 } SGK_CATCH_STATUS
 
-int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try {
+// sgk_ppo_epochs (one member, the handle's seed) and sgk_ppo_epochs_members: the same checks, the same kernel
+static int ppo_epochs_impl(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
   const void *need[] = {L->states, L->actions, L->returns, L->lengths, L->w1, L->b1, L->w2, L->b2, L->wa, L->ba, L->wc, L->bc,
@@ -1026,6 +1045,10 @@ int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try {
                                  "horizon >= 1, 1 <= n_trajectories < 2^31");
   if (sgk::ppo_epochs_lds_bytes(h->sh.n_cells, L->n_hidden) > 160u * 1024u)
     return fail(SGK_ERR_INVALID, "this n_cells / n_hidden does not fit the 160 KB of LDS the kernel works in");
+  if (n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)n_members);
+  if (L->n_trajectories % n_members != 0)
+    return fail(SGK_ERR_INVALID, "n_trajectories (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                (long long)L->n_trajectories, (int)n_members);
   sgk::PpoLearner d;
   d.states = L->states; d.actions = L->actions; d.returns = L->returns; d.lengths = L->lengths;
   d.horizon = L->horizon; d.n_hidden = L->n_hidden; d.batch = L->batch; d.n_epochs = L->n_epochs;
@@ -1040,8 +1063,14 @@ int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try {
   d.rows_out = reinterpret_cast<long long *>(L->rows_out);
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
   d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
-  SGK_HIP(sgk::launch_ppo_epochs(h->sh, d, h->stream));
+  SGK_HIP(sgk::launch_ppo_epochs(h->sh, d, h->stream, n_members, member_keys_dev));
   return SGK_OK;
+}
+
+int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try { return ppo_epochs_impl(h, L, 1, nullptr); } SGK_CATCH_STATUS
+
+int sgk_ppo_epochs_members(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev) try {
+  return ppo_epochs_impl(h, L, n_members, member_keys_dev);
 } SGK_CATCH_STATUS
 
 int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch) try {

@@ -149,8 +149,8 @@ __device__ __forceinline__ void bump_reset_count(int32_t *__restrict__ n_resets,
   if (HasEnvDraws<ENV>::value) (void)__hip_atomic_fetch_add(&n_resets[env], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// must be reached by all 64 lanes of the wave
-__device__ __forceinline__ void acc_flush(const EpisodeAcc &a, long long *__restrict__ slab) {
+// must be reached by all 64 lanes of the wave; `slot`: one metrics vector (the maxima initialised to LLONG_MIN)
+__device__ __forceinline__ void acc_flush_row(const EpisodeAcc &a, long long *__restrict__ slot) {
   if (__ballot(a.n_eps > 0) == 0ull) return;  // wave-uniform
   long long s_ret = wave_sum64(a.s_ret), s_perf = wave_sum64(a.s_perf), s_mpos = wave_sum64(a.s_mpos);
   long long n_eps = wave_sum64(a.n_eps), n_pos = wave_sum64(a.n_pos);
@@ -158,7 +158,6 @@ __device__ __forceinline__ void acc_flush(const EpisodeAcc &a, long long *__rest
   // every lane holds the wave totals; lane c forwards column c of the slot: one atomic instruction for the six sums and one
   // for the four maxima (instead of ten single-lane atomics in a row on the same 128-byte line)
   const int c = threadIdx.x & 63;
-  long long *slot = slab + (size_t)(blockIdx.x % SGK_METRIC_SLOTS) * SGK_METRICS_LEN;
   if (c < 6) {
     const long long v = c == SGK_M_SUM_RETURN ? s_ret : c == SGK_M_SUM_SAFETY ? s_perf : c == SGK_M_SUM_MARGIN ? s_ret - s_perf
                       : c == SGK_M_SUM_MARGIN_POS ? s_mpos : c == SGK_M_EPISODES ? n_eps : n_pos;
@@ -167,6 +166,10 @@ __device__ __forceinline__ void acc_flush(const EpisodeAcc &a, long long *__rest
     const int m = c == SGK_M_MAX_RETURN ? m_ret : c == SGK_M_MAX_SAFETY ? m_perf : c == SGK_M_MAX_MARGIN ? m_margin : m_mpos;
     if (c != SGK_M_MAX_MARGIN_POS || n_pos > 0) atomicMax(&slot[c], (long long)m);
   }
+}
+// the workgroup's slot of the handle's metrics slab
+__device__ __forceinline__ void acc_flush(const EpisodeAcc &a, long long *__restrict__ slab) {
+  acc_flush_row(a, slab + (size_t)(blockIdx.x % SGK_METRIC_SLOTS) * SGK_METRICS_LEN);
 }
 
 // The per-step kernel's episode metrics: the lanes that finished an episode ADD THEIR OWN figures to nine wave-private LDS words

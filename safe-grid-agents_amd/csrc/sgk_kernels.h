@@ -85,9 +85,12 @@ struct PolicyWeights {
 // mode 0: epsilon-greedy over the scores (DeepQAgent.act_explore); mode 1: Categorical(logits = scores).sample() (PPO)
 hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, uint8_t *actions, float *scores, double eps,
                              uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
-// n_steps of {forward, draw, env.step} in one launch; trajectory outputs optional ([n_steps][n]...); SGK_F_AUTO_RESET in flags
+// n_steps of {forward, draw, env.step} in one launch; trajectory outputs optional ([n_steps][n]...); SGK_F_AUTO_RESET in flags.
+// n_members > 1: `w` addresses member 0 of weight tensors stacked [n_members][...], member m acts in the envs m * n / n_members ..;
+// member_metrics: int64 [n_members][SGK_METRICS_LEN] each member's episodes are also booked in, or null
 hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights &w, double eps, uint64_t draw0, int32_t n_steps,
-                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st);
+                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
+                                 int n_members = 1, int64_t *member_metrics = nullptr);
 hipError_t launch_eps_greedy(const Shard &sh, int mode, const float *scores, uint8_t *actions, double eps, uint64_t draw,
                              const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
 // the conv Q-body's forward + act_explore in one launch (sgk_convq.hip; a labelled NON-parity option: the reference's DeepQAgent is an MLP)
@@ -160,7 +163,10 @@ struct PpoLearner {
   double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
 };
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden);
-hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st);
+// n_members > 1: one workgroup per member; every tensor of P but the rollout is stacked [n_members][...] and P addresses member 0;
+// member m draws its rows from the trajectories m * n_trajectories / n_members .. with the key member_keys[m] (null: the shard's seed)
+hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members = 1,
+                             const uint64_t *member_keys = nullptr);
 // PPOBaseAgent.learn for PPOCNNAgent (sgk_ppo_cnn.hip): tensors in registration order (network.0.0, network.1.0.0, bottleneck,
 // actor_cnn.0, actor_linear, critic_cnn.0, critic_linear; weight then bias), the old policy's first ten
 struct PpoCnnLearner {

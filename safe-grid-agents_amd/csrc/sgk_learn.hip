@@ -1253,6 +1253,10 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_multi_kernel(LearnArgs a, LearnSh
 // bonus, the backward pass (including the path of the policy loss into the critic through the normalised advantage, which
 // the reference's autograd graph has) and Adam. Same structure as dqn_sgd_kernel: one workgroup, activations in LDS, weight
 // matrices staged per phase, dense layers and weight gradients on fp32 MFMA.
+// The grid is one workgroup per MEMBER (sgk_ppo_epochs_members; one member = sgk_ppo_epochs): every tensor below but the rollout is
+// stacked [n_members][...] and the pointers address member 0; workgroup m moves them to its own slice, draws its rows from its own
+// trajectories m * E .. (m + 1) * E - 1 (rows stay global: t * N + trajectory) with its own Philox key, and runs the body as it is.
+// The workgroup fills a CU's LDS, so the members run one per CU.
 // ------------------------------------------------------------------------------------------------
 struct PpoArgs {
   // rollout: states int8 [T][N][K0], actions uint8 [T][N], returns float [N][T], lengths int32 [N]
@@ -1262,18 +1266,20 @@ struct PpoArgs {
   const int32_t *lengths;
   int32_t T;
   int64_t N;
+  int64_t E;  // trajectories per member (N with one member)
   // current network (torch layouts), updated in place; transposed trunk copies kept current; Adam state per tensor
   float *w1, *b1, *w2, *b2, *wa, *ba, *wc, *bc;  // wa [4][H], ba [4], wc [1][H], bc [1]
   float *w1t, *w2t;
   float *m[8], *v[8];  // order: w1, b1, w2, b2, wa, ba, wc, bc
   // old policy: transposed trunk weights, actor as it is
   const float *ow1t, *ob1, *ow2t, *ob2, *owa, *oba;
-  long long *step;   // Adam step counter (device); also the key of the minibatch draws
-  float *stats_out;  // [n_epochs][3]: policy loss, value loss, entropy; or null
-  const long long *rows;  // [n_epochs][batch] rows t * N + env to use instead of the random draws; or null
-  long long *rows_out;    // [n_epochs][batch] the rows each epoch used; or null
+  long long *step;   // Adam step counter (device), one per member; also the key of the minibatch draws
+  float *stats_out;  // [n_epochs][3] per member: policy loss, value loss, entropy; or null
+  const long long *rows;  // [n_epochs][batch] per member: rows t * N + env to use instead of the random draws; or null
+  long long *rows_out;    // [n_epochs][batch] per member: the rows each epoch used; or null
   int32_t batch, n_epochs;
   uint64_t seed;
+  const uint64_t *member_keys;  // [n_members] Philox keys of the members' draws; null: `seed` for every member
   float lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
 };
 
@@ -1348,6 +1354,23 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
   constexpr int MT = (H + 15) / 16, KT1 = (K0 + 15) / 16;
   constexpr int T2 = MT * MT + MT, T1 = MT * KT1 + MT;  // weight tiles + the bias tiles (column sums)
   constexpr int N2 = (T2 + LWG / 64 - 1) / (LWG / 64), N1 = (T1 + LWG / 64 - 1) / (LWG / 64);
+  {  // this member's slice of every stacked tensor (wave-uniform address arithmetic, once)
+    const size_t mb = blockIdx.x;
+    const size_t sz[8] = {(size_t)H * K0, (size_t)H, (size_t)H * H, (size_t)H, (size_t)4 * H, 4, (size_t)H, 1};
+    a.w1 += mb * sz[0]; a.b1 += mb * sz[1]; a.w2 += mb * sz[2]; a.b2 += mb * sz[3];
+    a.wa += mb * sz[4]; a.ba += mb * sz[5]; a.wc += mb * sz[6]; a.bc += mb * sz[7];
+    a.w1t += mb * sz[0]; a.w2t += mb * sz[2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { a.m[i] += mb * sz[i]; a.v[i] += mb * sz[i]; }
+    a.ow1t += mb * sz[0]; a.ob1 += mb * sz[1]; a.ow2t += mb * sz[2]; a.ob2 += mb * sz[3]; a.owa += mb * sz[4]; a.oba += mb * sz[5];
+    a.step += mb;
+    const size_t per_epoch = mb * (size_t)a.n_epochs;
+    if (a.stats_out) a.stats_out += per_epoch * 3;
+    if (a.rows) a.rows += per_epoch * (size_t)a.batch;
+    if (a.rows_out) a.rows_out += per_epoch * (size_t)a.batch;
+    if (a.member_keys) a.seed = a.member_keys[mb];
+  }
+  const long long traj0 = (long long)blockIdx.x * a.E;  // this member's first trajectory
   const long long step0 = *a.step;
   {
     const int t = t0;
@@ -1380,7 +1403,7 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
     for (int round = 0; round < 64 && !found; ++round) {
       uint32_t x[4];
       philox4x32_10((uint32_t)(b * 16 + c), (uint32_t)round, (uint32_t)e_step, 5u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), x);
-      const long long n_c = (long long)__umul64hi(((unsigned long long)x[0] << 32) | x[1], (unsigned long long)a.N);
+      const long long n_c = traj0 + (long long)__umul64hi(((unsigned long long)x[0] << 32) | x[1], (unsigned long long)a.E);
       const int t_c = (int)__umulhi(x[2], (uint32_t)a.T);
       const bool ok = t_c < a.lengths[n_c];
       const unsigned long long mask = __ballot(ok);
@@ -1801,15 +1824,17 @@ extern "C" __attribute__((visibility("default"))) int sgk_debug_learn_stamps(uns
 
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden) { return ppo_lds_bytes((n_cells + 3) & ~3, n_hidden); }
 
-hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st) {
+hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys) {
   (void)hipGetLastError();
   if (P.batch < 2 || P.batch > LB || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 || P.n_trajectories >= (1ll << 31))
     return hipErrorInvalidValue;
+  if (n_members < 1 || P.n_trajectories % n_members != 0) return hipErrorInvalidValue;
   const size_t lds = ppo_epochs_lds_bytes(sh.n_cells, P.n_hidden);
   if (lds > 160u * 1024u) return hipErrorInvalidValue;
   PpoArgs a;
   a.states = P.states; a.actions = P.actions; a.returns = P.returns; a.lengths = P.lengths;
-  a.T = P.horizon; a.N = P.n_trajectories;
+  a.T = P.horizon; a.N = P.n_trajectories; a.E = P.n_trajectories / n_members;
+  a.member_keys = member_keys;
   a.w1 = P.w1; a.b1 = P.b1; a.w2 = P.w2; a.b2 = P.b2; a.wa = P.wa; a.ba = P.ba; a.wc = P.wc; a.bc = P.bc;
   a.w1t = P.w1t; a.w2t = P.w2t;
   for (int i = 0; i < 8; ++i) { a.m[i] = P.m[i]; a.v[i] = P.v[i]; }
@@ -1827,7 +1852,7 @@ hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t s
       if (ae != hipSuccess) return ae;                                                                                     \
       opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
     }                                                                                                                      \
-    ppo_epochs_kernel<K0V, HV><<<dim3(1), dim3(LWG), lds, st>>>(a);                                                        \
+    ppo_epochs_kernel<K0V, HV><<<dim3(n_members), dim3(LWG), lds, st>>>(a);                                                \
   } while (0)
 #define SGK_PPO_LAUNCH_K(K0V)                                                                                              \
   do {                                                                                                                     \

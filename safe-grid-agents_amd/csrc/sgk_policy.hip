@@ -1,6 +1,7 @@
 // sgk_policy.hip -- the network-facing kernels: action draws on scores / logits (DeepQAgent.act_explore, reference
 // value.py:94-111; PPOBaseAgent.act_explore, policy_base.py:54-64), the fused MLP forward + draw on the matrix cores
 // (value.py:89-111,148-158; policy_mlp.py:17-43) and PPOBaseAgent.get_discounted_returns (policy_base.py:179-186).
+#include <algorithm>
 #include <atomic>
 
 #include "sgk_device.h"
@@ -321,6 +322,11 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_mfma_kernel(const int8_t *__r
 // changed. Everything a wave touches in the loop is its own (its 32 tile rows, its lanes' registers), so the step loop has
 // no workgroup barrier. Per step and wave: 526 MFMAs (H = 100), one Philox block, one table lookup, <= 4 LDS byte writes,
 // and the optional trajectory stores (board rows as dwords, one action byte, one 4-byte record per env).
+// A launch serves n_members independent policies (sgk_policy_rollout_members; 1 = the shared policy of sgk_policy_rollout): member m
+// owns the envs m * member_envs .. (m + 1) * member_envs - 1 and the m-th slice of each stacked weight tensor. A workgroup belongs
+// to ONE member for the whole launch (member_wgs consecutive workgroups each), stages that member's weights and walks that member's
+// ceil(member_envs / 128) tiles only, so a tile never straddles two members. Env indices -- RNG keys, trajectory columns, episode
+// arrays -- stay the shard's own.
 // ------------------------------------------------------------------------------------------------
 struct RolloutArgs {
   StepArgs env;              // state / rec / episode arrays / metrics / rules / n / seed / env_base / flags
@@ -331,6 +337,9 @@ struct RolloutArgs {
   int8_t *states_out;        // [n_steps][n][K0] boards the policy acted on, or null
   uint8_t *actions_out;      // [n_steps][n] or null
   uint32_t *recs_out;        // [n_steps][n] step records or null
+  int64_t member_envs;       // envs per member (n with one member)
+  int32_t member_wgs;        // workgroups per member: the grid is n_members * member_wgs
+  long long *member_metrics; // [n_members][SGK_METRICS_LEN]: each member's own episode sums / counts / maxima, or null
 };
 
 template <int ENV, int H, int MODE>
@@ -348,7 +357,14 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a)
   float *lb3 = lb2 + G::B;
   int8_t *tile = reinterpret_cast<int8_t *>(lb3 + 16);                      // [PMFMA_ENVS][K0]
   SgkRules &R = *reinterpret_cast<SgkRules *>(tile + 2 * PMFMA_ENVS * K0);  // behind the (here unused) second tile buffer
-  const PolicyWeights &w = a.w;
+  const int member = (int)blockIdx.x / a.member_wgs, member_wg = (int)blockIdx.x - member * a.member_wgs;
+  PolicyWeights w = a.w;  // this member's slice of the stacked tensors
+  w.w1t += (size_t)member * (K0 * H);
+  w.b1 += (size_t)member * H;
+  w.w2 += (size_t)member * (H * H);
+  w.b2 += (size_t)member * H;
+  w.w3t += (size_t)member * (H * 4);
+  w.b3 += (size_t)member * 4;
   // weights in operand order (same arrangement as policy_mfma_kernel; staged once per launch, so plainly)
   for (int i = threadIdx.x; i < G::W1; i += PMFMA_WG) {
     const int l = i & 63, s = (i >> 6) % KS1, mt = (i >> 6) / KS1;
@@ -385,12 +401,13 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a)
   const int wave_env = wave * PMFMA_NT * 16;
   const bool owner = lane < 32;  // lanes 32..63 only take part in the MFMAs and the row stores
   const int64_t n = a.env.n;
-  const int64_t n_tiles = (n + PMFMA_ENVS - 1) / PMFMA_ENVS;
+  const int64_t env0 = (int64_t)member * a.member_envs, env_end = env0 + a.member_envs;  // this member's envs
+  const int64_t n_tiles = (a.member_envs + PMFMA_ENVS - 1) / PMFMA_ENVS;
   EpisodeAcc acc;
   acc_init(acc);
-  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const int64_t env = t * PMFMA_ENVS + wave_env + (lane & 31);
-    const bool valid = owner && env < n;
+  for (int64_t t = member_wg; t < n_tiles; t += a.member_wgs) {
+    const int64_t env = env0 + t * PMFMA_ENVS + wave_env + (lane & 31);
+    const bool valid = owner && env < env_end;
     EnvState s = initial_state(R);
     if (valid) s = unpack_state(a.env.state[env]);
     load_episode_index<ENV>(s, a.env.n_resets, env, valid);
@@ -400,8 +417,9 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a)
     for (int k = 0; k < a.n_steps; ++k) {
       __builtin_amdgcn_wave_barrier();  // the rows written by lanes 0..31 are read by all 64 lanes below
       if (a.states_out) {  // the boards the policy is about to act on: this wave's 32 rows are contiguous in the output
-        const int64_t first = t * PMFMA_ENVS + wave_env;
-        const int rows = (int)max((int64_t)0, min((int64_t)32, n - first));
+        // (a member whose first row is not dword aligned takes the byte path below; its last wave stops at the member's end)
+        const int64_t first = env0 + t * PMFMA_ENVS + wave_env;
+        const int rows = (int)max((int64_t)0, min((int64_t)32, env_end - first));
         int8_t *dst = a.states_out + ((int64_t)k * n + first) * K0;
         const int8_t *src = tile + wave_env * K0;
         // SGK_F_MASK_FINISHED: rows of envs whose episode is over (bit r = row r of this wave) are stored as zeros
@@ -457,6 +475,7 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a)
     __builtin_amdgcn_wave_barrier();
   }
   acc_flush(acc, a.env.metrics);
+  if (a.member_metrics) acc_flush_row(acc, a.member_metrics + (size_t)member * SGK_METRICS_LEN);  // the same reduction, this member's row
 }
 
 template <int ENV, int H>
@@ -561,8 +580,10 @@ hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, 
 }
 
 hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights &w, double eps, uint64_t draw0, int32_t n_steps,
-                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st) {
+                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
+                                 int n_members, int64_t *member_metrics) {
   (void)hipGetLastError();
+  if (n_members < 1 || sh.n % n_members != 0) return hipErrorInvalidValue;
   RolloutArgs a;
   a.env = make_step_args(sh, nullptr, flags);
   a.w = w;
@@ -572,7 +593,11 @@ hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights 
   a.states_out = states_out;
   a.actions_out = actions_out;
   a.recs_out = recs_out;
-  int grid = grid_for((sh.n + PMFMA_ENVS - 1) / PMFMA_ENVS, sh.n_cus);
+  a.member_envs = sh.n / n_members;
+  // a member's workgroups: one per tile while all members' fit the CUs (one member: exactly the shared-policy grid), at least one
+  a.member_wgs = grid_for((a.member_envs + PMFMA_ENVS - 1) / PMFMA_ENVS, std::max(sh.n_cus / n_members, 1));
+  a.member_metrics = reinterpret_cast<long long *>(member_metrics);
+  const int grid = n_members * a.member_wgs;
 #define SGK_ROLLOUT_LAUNCH_M(E, HID, MODE)                                                                                 \
   do {                                                                                                                     \
     constexpr size_t lds = policy_rollout_lds_bytes<E, HID>();                                                             \

@@ -4,7 +4,7 @@ default log dir runs/<env>/<agent>/<baseline|corrupt>/<seed>."""
 import os
 import random
 
-from .trainer import prepare_parser, train, train_batched
+from .trainer import members_n_envs, prepare_parser, train, train_batched
 
 
 def _spawn_ranks(n, argv):
@@ -25,6 +25,8 @@ def main(argv=None):
     import sys
 
     args = prepare_parser().parse_args(argv)
+    if getattr(args, "members", 0):
+        members_n_envs(args)  # --members M: N = M x rollouts
     if getattr(args, "devices", 1) > 1 and "WORLD_SIZE" not in os.environ:
         if getattr(args, "n_envs", 0) <= 0:
             raise SystemExit("--devices shards the batched trainer: give -N/--n-envs too")

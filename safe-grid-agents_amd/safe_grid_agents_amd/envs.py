@@ -797,6 +797,59 @@ class BatchedGridworldEnv:
         _lib.check(self.lib.sgk_ppo_epochs(self._h.ptr, ctypes.byref(learner)))
         self._sync_lib_to_torch()
 
+    def _member_weights_arg(self, weights, n_members):
+        """sgk_mlp_weights addressing member 0 of float32 device tensors stacked on a leading member axis: w1t [M, cells, H], b1 [M, H],
+        w2 [M, H, H], b2 [M, H], w3t [M, H, 4], b3 [M, 4]."""
+        try:
+            h = int(weights["b1"].shape[-1])
+        except (KeyError, TypeError, AttributeError, IndexError):
+            raise ValueError("weights must be a dict of stacked float32 device tensors w1t, b1, w2, b2, w3t, b3") from None
+        m = int(n_members)
+        shapes = {"w1t": (m, self.n_cells, h), "b1": (m, h), "w2": (m, h, h), "b2": (m, h), "w3t": (m, h, 4), "b3": (m, 4)}
+        for k, shape in shapes.items():
+            if k not in weights:
+                raise ValueError("weights lack %r" % k)
+            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
+        return _lib.SgkMlpWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1t", "b1", "w2", "b2", "w3t", "b3")), h)
+
+    def policy_rollout_members(self, weights, n_members, n_steps, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False,
+                               states=None, actions=None, recs=None, mask_finished=False, member_metrics=None):
+        """policy_rollout for n_members independent policies in ONE HIP launch (sgk_policy_rollout_members): member m acts in the envs
+        m * E .. (m + 1) * E - 1 (E = N / n_members) with slice m of `weights`, tensors stacked on a leading member axis (see
+        _member_weights_arg). Outputs as for policy_rollout; member_metrics: int64 [n_members, 16] on this device that each member's
+        episodes are also booked in (sums added, maxima raised), or None."""
+        n_members = int(n_members)
+        if n_members < 1 or self.n_envs % n_members:
+            raise ValueError("n_envs (%d) is not a multiple of n_members (%d)" % (self.n_envs, n_members))
+        w = self._member_weights_arg(weights, n_members)
+        if mode not in ("greedy", "sample"):
+            raise ValueError("mode must be 'greedy' or 'sample'")
+
+        def ptr(t, shape, what, dtype):
+            if t is None:
+                return None
+            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
+
+        n = self.n_envs
+        args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
+                ptr(recs, (n_steps, n, 4), "recs", "int8"), ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"))
+        self._version += 1
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_policy_rollout_members(
+            self._h.ptr, ctypes.byref(w), n_members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
+            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
+        self._sync_lib_to_torch()
+
+    def ppo_epochs_members(self, learner, n_members, member_keys=None):
+        """One PPO learn() call of n_members independent PPOMLPAgents in ONE HIP launch (sgk_ppo_epochs_members); `learner` is a filled
+        _lib.SgkPpoLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None."""
+        kp = None
+        if member_keys is not None:
+            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_ppo_epochs_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp))
+        self._sync_lib_to_torch()
+
     def ppo_cnn_epochs(self, learner):
         """All epochs of one PPOCNNAgent learn() call on the device, three HIP launches per epoch (sgk_ppo_cnn_epochs); `learner` is a
         filled _lib.SgkPpoCnnLearner whose device pointers (the workspace among them) the caller keeps alive."""

@@ -265,6 +265,18 @@ def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buf
             states[t].copy_(boards)
             env.step(actions[t], auto_reset=False)
             recs[t].copy_(record)
+    return rollout_from_records(env, buf, discount, cheat=cheat, masked=fused is not None)
+
+
+def rollout_from_records(env, buf, discount, cheat=False, masked=False):
+    """The second half of batched_gather_rollout: lengths, rewards and the discounted returns from the T step records in `buf`
+    (rollout_buffers), the env reset. masked: the kernel that wrote states / actions already stored zeros past an episode's end."""
+    import torch
+
+    states, actions, recs = buf["states"], buf["actions"], buf["recs"]
+    rewards, returns, lengths = buf["rewards"], buf["returns"], buf["lengths"]
+    T, n = actions.shape
+    dev = actions.device
     # a finished env idles: its later records read (0, 0, done, .), so everything per-episode follows from the done flags
     finished_steps = (recs[:, :, 2] != 0).sum(0, dtype=torch.int32)  # done stays set from the last step of the episode on
     lengths.copy_(torch.clamp(T - finished_steps + 1, max=T))
@@ -273,12 +285,12 @@ def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buf
         rewards.copy_(recs[:, :, 1 if cheat else 0].t().to(torch.float64) * env.reward_scale)
     else:
         rewards.copy_(recs[:, :, 1 if cheat else 0].t())
-    if cheat or fused is None:
+    if cheat or not masked:
         live = torch.arange(T, device=dev).unsqueeze(1) < lengths.unsqueeze(0)  # [T, N]
         if cheat:
             actions.copy_(recs[:, :, 3].view(torch.uint8))
         actions.mul_(live)
-        if fused is None:
+        if not masked:
             states.mul_(live.unsqueeze(2))
     returns.zero_()
     env.discounted_returns(rewards, discount, lengths=lengths, out=returns)
@@ -318,3 +330,15 @@ def batched_tabq_learn(agent, env, n_steps, cheat=False, fused=True, chunk=100):
             agent.learn_steps(k, cheat=cheat)
             done += k
     return BatchMetrics(env.metrics(), env.reward_scale)
+
+
+def population_ppo_learn(pop, env, history=None, cheat=False):
+    """batched_ppo_learn for a BatchedPPOPopulation: every member gathers one rollout of its E episodes under its own old policy
+    (one launch), runs its epochs (one launch) and syncs. Returns (per-member BatchMetrics of the gathered episodes, their aggregate)."""
+    env.metrics_reset()
+    pop.reset_member_metrics()
+    rollout = pop.gather_rollout(cheat=cheat)
+    members, total = pop.member_batch_metrics(), BatchMetrics(env.metrics(), env.reward_scale)
+    pop.learn(rollout, history)
+    pop.sync()
+    return members, total

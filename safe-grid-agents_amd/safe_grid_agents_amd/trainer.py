@@ -34,6 +34,9 @@ _CORE_FLAGS = [
     # RCCL metrics all-reduce per reporting period). `python -m safe_grid_agents_amd --devices G ...` starts the G ranks itself;
     # under torch.distributed.run the launcher's WORLD_SIZE decides and this flag is only checked against it.
     ("devices", "G", dict(type=int, default=1)),
+    # extension: with ppo-mlp, M independent agents (BatchedPPOPopulation) of `--rollouts` envs each in one batch of N = M x rollouts
+    # envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree.
+    ("members", "M", dict(type=int, default=0)),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -169,8 +172,13 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
     from . import dist as sdist
     from .agents import BatchedTabularQAgent
-    from .loops import batched_default_eval, batched_ppo_learn
+    from .loops import batched_default_eval, batched_ppo_learn, population_ppo_learn
     from .ppo import BatchedPPOAgent
+    from .ppo_population import BatchedPPOPopulation
+
+    members = int(getattr(args, "members", 0) or 0)
+    if members:
+        members_n_envs(args)  # N = M x rollouts
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -178,6 +186,8 @@ def train_batched(args, writer_factory=None, reporter=_noop):
                          "which starts them, or torch.distributed.run --nproc-per-node %d" % (
                              args.devices, args.devices, world, args.devices, args.devices))
     if world > 1:
+        if members:
+            raise KeyError("--members runs on one GPU (sharding a population over GPUs is not built)")
         if args.agent_alias in ("ppo-mlp", "ppo-cnn"):
             raise KeyError("train_batched shards independent agents (tabular-q, random) over GPUs; %r shares one policy"
                            % (args.agent_alias,))
@@ -194,6 +204,8 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     sdist.library_comm(env)  # (several ranks under nccl) the metrics all-reduce's RCCL communicator, before the first flush
     if args.agent_alias == "tabular-q":
         agent = BatchedTabularQAgent(env, args)
+    elif members:
+        agent = BatchedPPOPopulation(env, args, members)
     elif args.agent_alias in ("ppo-mlp", "ppo-cnn"):
         import torch
 
@@ -216,12 +228,17 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         agent = None
     else:
         raise KeyError("train_batched supports tabular-q, deep-q, ppo-mlp, ppo-cnn and random, not %r" % (args.agent_alias,))
-    ppo = isinstance(agent, BatchedPPOAgent)
+    ppo = isinstance(agent, (BatchedPPOAgent, BatchedPPOPopulation))
     deepq = args.agent_alias == "deep-q"
     history = {"writer": writer, "t": 0, "t_learn": 0}
     period = 0
     for episode in range(1, args.episodes + 1):
-        if ppo:
+        if members:  # every member's rollout + epochs: two launches; the aggregate meters and the spread over the members
+            per_member, bm = population_ppo_learn(agent, env, history, cheat=args.cheat)
+            history["t"] += horizon
+            for tag, name in (("Train/member_return", "returns"), ("Train/member_safety", "safeties")):
+                writer.add_histogram(tag, np.array([m.meter(name)["avg"] for m in per_member], dtype=np.float64), episode)
+        elif ppo:
             bm = batched_ppo_learn(agent, env, history, cheat=args.cheat)
             history["t"] += horizon
         else:
@@ -256,6 +273,22 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     return agent, env
 
 
+def members_n_envs(args):
+    """--members M: the batch is N = M x rollouts envs. Sets args.n_envs; an explicit -N that disagrees, or another agent than ppo-mlp,
+    stops the run with a message."""
+    members = int(args.members)
+    if members < 1:
+        raise SystemExit("--members must be >= 1")
+    if args.agent_alias != "ppo-mlp":
+        raise SystemExit("--members runs a population of ppo-mlp agents, not %r" % (args.agent_alias,))
+    n = members * int(args.rollouts)
+    if int(getattr(args, "n_envs", 0) or 0) not in (0, n):
+        raise SystemExit("--members %d with --rollouts %d is a batch of %d envs; -N %d disagrees (leave -N out)"
+                         % (members, int(args.rollouts), n, args.n_envs))
+    args.n_envs = n
+    return n
+
+
 def _batched_eval(agent, env, args, writer, period, rank, sdist):
     from .loops import batched_default_eval
 
@@ -263,7 +296,10 @@ def _batched_eval(agent, env, args, writer, period, rank, sdist):
         print("#### EVAL ####")
     if hasattr(agent, "check_hash_tables"):
         agent.check_hash_tables()  # levels without a perfect hash of their boards: a full table is an error, not a silent state
-    batched_default_eval(agent, env, args.eval_timesteps)
+    if hasattr(agent, "member_metrics"):  # a population: the two greedy phases through the members rollout
+        agent.evaluate(args.eval_timesteps)
+    else:
+        batched_default_eval(agent, env, args.eval_timesteps)
     sdist.global_metrics(env).write(writer, period, prefix="Evaluation/")
     env.reset()
     return period + 1
