@@ -13,6 +13,10 @@ torch on .double() tensors with autograd (or on .float() ones: the float32 yards
   adam64        one element-wise Adam step with torch's formulas (the comment above adam_scalar in csrc/sgk_learn.hip), amsgrad when
                 a vmax is given. lr, beta1, beta2 and eps are taken as the float32 values the kernels receive; 1 - beta is then exact
                 in float32 (Sterbenz), so (1 - beta1) here is the kernel's own factor.
+  ppo_chain64   n epochs of ppo_epoch64 + adam64 in a row, as one sgk_ppo_epochs launch of n epochs runs them (the yardstick: the
+                epochs in float32 with torch.optim.Adam itself; stale=True: the emulation of a launch whose epochs read the previous
+                update too early), with the seeded rows, Adam state and ragged / sparse rollouts (ppo_ragged_inputs) of
+                tests/test_gpu_ppo_epoch_chain.py.
 
 The discount is taken as its float32 value as well: torch's float32 run and the kernel both multiply by float32(discount).
 """
@@ -524,3 +528,139 @@ def cnn_stat_pair(case, r64, i, got):
 
 def cnn_stat_err(case, r64, i, got):
     return rel_err(*cnn_stat_pair(case, r64, i, got))
+
+
+# ---- the epoch chain: sgk_ppo_epochs' n_epochs updates in one launch (tests/test_gpu_ppo_epoch_chain.py) -----------------------------
+CHAIN_EPOCHS, CHAIN_STEP0 = 4, 4999
+CHAIN_STATE_SEED = 91
+CHAIN_STALE_FACTOR = 10.0         # how many limits the stale-epoch emulation must lie from the true chain, on every trunk tensor
+TRUNK_TENSORS = ("w1", "b1", "w2", "b2")
+RAGGED_HORIZON, SPARSE_HORIZON = 5, 16
+# the cases of the float64 chain (the seeds: tests/test_learner_reference_cpu.py::test_a_stale_epoch_lies_far_outside_the_chains_limit)
+CHAIN_CASES = [PpoCase("SideEffectsSokoban-v0", 100, 64, 2400), PpoCase("BoatRace-v0", 64, 64, 2401),
+               PpoCase("DistributionalShift-v0", 100, 33, 2402)]
+
+
+def ragged_lengths(n):
+    """Lengths cycling through 0, 1, 2, 5 (RAGGED_HORIZON = 5): a trajectory of every kind among any four neighbours."""
+    return np.array([0, 1, 2, 5], dtype=np.int32)[np.arange(n) % 4]
+
+
+def sparse_lengths(n=N_ENVS):
+    """Four trajectories of SPARSE_HORIZON steps (spread over the four waves' worth of columns), every other one empty: one (t, trajectory)
+    candidate in 16 is valid, so a sample's 16 candidates all miss with probability (15/16)^16 = 0.36 and a second Philox round runs."""
+    lengths = np.zeros(n, dtype=np.int32)
+    lengths[[5, 22, 39, n - 1]] = SPARSE_HORIZON
+    return lengths
+
+
+def ppo_ragged_inputs(case, horizon, lengths):
+    """ppo_inputs' rollout and networks at [horizon][len(lengths)] with the given episode lengths (the entries past a trajectory's length
+    hold seeded data as well: a row drawn from there changes the result). No rows: the kernel draws them."""
+    rng = np.random.default_rng(case.seed + 7000)
+    lengths = np.asarray(lengths, dtype=np.int32)
+    k0, h, n = ENV_CELLS[case.env], case.hidden, len(lengths)
+    assert lengths.max() <= horizon and lengths.any()
+    d = {"states": rng.integers(0, 6, (horizon, n, k0)).astype(np.int8),
+         "actions": rng.integers(0, 4, (horizon, n)).astype(np.uint8),
+         "returns": rng.uniform(-5.0, 5.0, (n, horizon)).astype(np.float32),
+         "lengths": lengths}
+    old = _linear(rng, h, k0) + _linear(rng, h, h) + _linear(rng, 4, h) + _linear(rng, 1, h)
+    d["old"] = old
+    d["cur"] = [(p + np.float32(0.05) * rng.standard_normal(p.shape).astype(np.float32)).astype(np.float32) for p in old]
+    return d
+
+
+def chain_rows(case, d, epochs):
+    """The caller's rows of a chain on ppo_inputs' dense rollout: epoch 0 takes the case's own minibatch (both clamp branches, a
+    duplicate), the later epochs seeded rows; int64 [epochs, batch]. Every pair of the dense rollout is valid, so these are both the
+    flat rows t * N + trajectory and the indices into the valid pairs that BatchedPPOAgent.learn takes."""
+    rng = np.random.default_rng(case.seed + 500)
+    n = SLICES * N_ENVS
+    # (below four rows no duplicates: two equal rows of two make the advantages' std 0)
+    rows = np.stack([rng.integers(0, n, case.batch) if case.batch >= 4 else rng.choice(n, case.batch, replace=False) for _ in range(epochs)])
+    rows[0] = d["rows"]
+    return rows.astype(np.int64)
+
+
+def chain_state(case, d, rows0):
+    """(m, v), float32: inject_adam_state around a gradient of constant magnitude per tensor, the largest element of the float64
+    gradient of the chain's first epoch. (Around the gradient itself, element by element, v = u g^2 is tiny wherever g is while m ~
+    max|g| is not: one step then moves such elements by thousands of lr, which a one-step test bears and a chain does not -- after two
+    epochs the logits saturate and the entropy is NaN in float64 as well.) So m ~ N(0, max|g|), v = u max|g|^2 with u log-uniform in
+    [1e-3, 1e3]: steps of ~0.03 lr to ~100 lr in every tensor."""
+    g = ppo_epoch64(d["cur"], d["old"][:6], *ppo_gather(d, rows0), **_ppo_loss_kw())["grads"]
+    return inject_adam_state([np.full(x.shape, np.abs(x).max()) for x in g], CHAIN_STATE_SEED + case.seed, False)[:2]
+
+
+class _TorchAdam32:
+    """torch.optim.Adam itself (the single-tensor implementation) on float32 copies of the tensors, from the given moments and step
+    count: the Adam of the float32 yardstick chain. lr, betas and eps are the float32 values the kernels receive, as in adam64."""
+
+    def __init__(self, w, m, v, step0, lr):
+        f = lambda x: float(np.float32(x))  # noqa: E731
+        self.p = [torch.nn.Parameter(torch.as_tensor(np.array(x, dtype=np.float32))) for x in w]
+        self.opt = torch.optim.Adam(self.p, lr=f(lr), betas=(f(BETA1), f(BETA2)), eps=f(EPS), foreach=False, fused=False)
+        for p, m_, v_ in zip(self.p, m, v):
+            self.opt.state[p] = {"step": torch.tensor(float(step0)), "exp_avg": torch.as_tensor(np.array(m_, dtype=np.float32)),
+                                 "exp_avg_sq": torch.as_tensor(np.array(v_, dtype=np.float32))}
+
+    def step(self, grads):
+        for p, g in zip(self.p, grads):
+            p.grad = torch.as_tensor(np.asarray(g, dtype=np.float32))
+        self.opt.step()
+        return [p.detach().numpy().copy() for p in self.p]
+
+
+def ppo_chain64(d, rows_per_epoch, state, step0, dtype=torch.float64, stale=False):
+    """len(rows_per_epoch) times ppo_epoch64 followed by Adam (adam64; torch.optim.Adam on float32 tensors with dtype float32: the yardstick) from d["cur"], the Adam
+    state (m, v) (None: zeros) and `step0` steps done: {"params": the eight tensors after every epoch, "stats": the three scalars of
+    every epoch}. stale: epoch e >= 1 takes its gradients at the parameters epoch e - 1 started from (what a launch computes whose
+    epochs re-read the previous update's stores too early) and applies them to the current ones -- the emulation the CPU suite holds
+    the chain test's limit against."""
+    f64 = dtype == torch.float64
+    ftype = np.float64 if f64 else np.float32
+    w = [np.asarray(p, dtype=ftype) for p in d["cur"]]
+    m, v = ([np.zeros_like(p) for p in w] for _ in range(2)) if state is None else ([np.asarray(x, dtype=ftype) for x in s] for s in state)
+    out = {"params": [], "stats": []}
+    t32 = None if f64 else _TorchAdam32(w, m, v, step0, PPO_HYPER["lr"])
+    before = w
+    for e, rows in enumerate(rows_per_epoch):
+        r = ppo_epoch64(before if stale and e else w, d["old"][:6], *ppo_gather(d, np.asarray(rows)), dtype=dtype, **_ppo_loss_kw())
+        before = w
+        if f64:
+            new = [adam64(w[i], m[i], v[i], None, g, step0 + e + 1, PPO_HYPER["lr"]) for i, g in enumerate(r["grads"])]
+            w, m, v = [n[0] for n in new], [n[1] for n in new], [n[2] for n in new]
+        else:
+            w = t32.step(r["grads"])
+        out["params"].append(w)
+        out["stats"].append(r["stats"])
+    return out
+
+
+def chain_err(got, want, w0):
+    """max|got - want| / max|want - w0|: a tensor's error relative to its total movement over the chain."""
+    got, want, w0 = (np.asarray(x, dtype=np.float64) for x in (got, want, w0))
+    return float(np.abs(got - want).max() / np.abs(want - w0).max())
+
+
+def chain_limit(err_t, want, w0, epochs):
+    """max(8 err_t, epochs x 2^-23 max|w0| / max|want - w0|): the project's margin over the torch-float32 chain's own figure, and never
+    below one rounding of the parameter per epoch."""
+    want, w0 = np.asarray(want, dtype=np.float64), np.asarray(w0, dtype=np.float64)
+    return max(8.0 * err_t, epochs * ULP * float(np.abs(w0).max()) / float(np.abs(want - w0).max()))
+
+
+@functools.lru_cache(maxsize=None)
+def chain_yardstick(case):
+    """(inputs, rows [CHAIN_EPOCHS, batch], Adam state, the float64 chain, the torch-float32 chain's err_t per tensor (chain_err after
+    the last epoch) and per statistic ("policy_loss 2": rel_err in epoch 2)) of a chain case; once per process."""
+    d = ppo_inputs(case)
+    rows = chain_rows(case, d, CHAIN_EPOCHS)
+    state = chain_state(case, d, rows[0])
+    c64, c32 = ppo_chain64(d, rows, state, CHAIN_STEP0), ppo_chain64(d, rows, state, CHAIN_STEP0, dtype=torch.float32)
+    err_t = {k: chain_err(a, b, w0) for k, a, b, w0 in zip(PPO_TENSORS, c32["params"][-1], c64["params"][-1], d["cur"])}
+    for e in range(CHAIN_EPOCHS):
+        for i, k in enumerate(("policy_loss", "value_loss", "entropy")):
+            err_t["%s %d" % (k, e)] = rel_err(c32["stats"][e][i], c64["stats"][e][i])
+    return d, rows, state, c64, err_t

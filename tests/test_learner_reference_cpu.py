@@ -269,3 +269,74 @@ def test_conv_case_list_covers_what_the_issue_names():
     assert all(R.ppo_cnn_hyper(c) == R.PPO_HYPER for c in cases if c.variant != "defaults")
     assert len({c.seed for c in cases}) == len(cases) and not {c.seed for c in cases} & {c.seed for c in R.PPO_CASES + R.DQN_CASES}
     assert {c.channels for c in R.PLUMBING_CASES} == {5, 8} and (R.CNN_T, R.CNN_N) == (3, 37)
+
+
+# ---- the epoch chain (tests/test_gpu_ppo_epoch_chain.py) -----------------------------------------------------------------------------
+def test_ppo_chain64_of_one_epoch_is_ppo_epoch64_then_adam64():
+    """ppo_chain64 with one epoch against the step the one-epoch tests take (ppo_epoch64's gradients through adam64 at step0 + 1, from the
+    same injected state), exactly; and with two epochs, the second epoch is that step again from the first one's results."""
+    case = R.CHAIN_CASES[0]
+    d, rows, state, c64, _ = R.chain_yardstick(case)
+    kw = {k: R.PPO_HYPER[k] for k in ("clipping", "critic_coeff", "entropy_bonus")}
+    one = R.ppo_chain64(d, rows[:1], state, R.CHAIN_STEP0)
+    ref = R.ppo_epoch64(d["cur"], d["old"][:6], *R.ppo_gather(d, rows[0]), **kw)
+    assert one["stats"] == [ref["stats"]] and len(one["params"]) == 1
+    stepped = [R.adam64(d["cur"][i], state[0][i], state[1][i], None, g, R.CHAIN_STEP0 + 1, R.PPO_HYPER["lr"]) for i, g in enumerate(ref["grads"])]
+    for k, got, want in zip(R.PPO_TENSORS, one["params"][0], stepped):
+        assert got.dtype == np.float64 and (got == want[0]).all() and np.abs(got - d["cur"][R.PPO_TENSORS.index(k)]).max() > 0, k
+    for got, want in zip(c64["params"][0], one["params"][0]):
+        assert (got == want).all()
+    ref2 = R.ppo_epoch64(one["params"][0], d["old"][:6], *R.ppo_gather(d, rows[1]), **kw)
+    assert c64["stats"][1] == ref2["stats"]
+    for i, g in enumerate(ref2["grads"]):
+        want = R.adam64(one["params"][0][i], stepped[i][1], stepped[i][2], None, g, R.CHAIN_STEP0 + 2, R.PPO_HYPER["lr"])[0]
+        assert (c64["params"][1][i] == want).all(), i
+    zero = R.ppo_chain64(d, rows[:1], None, 0)  # no state: zero moments, the first Adam step moves an element by lr |g| / (|g| + eps)
+    moved = np.abs(zero["params"][0][2] - d["cur"][2])
+    lr = float(np.float32(R.PPO_HYPER["lr"]))
+    assert (moved <= lr * (1 + 1e-12)).all() and np.median(moved[ref["grads"][2] != 0]) > 0.999 * lr
+
+
+@pytest.mark.parametrize("case", R.CHAIN_CASES, ids=R.case_id)
+def test_a_stale_epoch_lies_far_outside_the_chains_limit(case):
+    """What keeps the float64 chain test from being vacuous: the same chain with every epoch e >= 1 taking its gradients at the
+    parameters epoch e - 1 started from (ppo_chain64(stale=True), in float64) lies at least CHAIN_STALE_FACTOR = 10 times the GPU test's
+    limit away from the true chain, in that test's metric, on every trunk tensor (here on the heads as well). Also: torch-float32's own
+    error on every epoch's statistics stays below the cap / 8, as for the one-epoch cases, and the chain stays finite."""
+    d, rows, state, c64, err_t = R.chain_yardstick(case)
+    stale = R.ppo_chain64(d, rows, state, R.CHAIN_STEP0, stale=True)
+    assert len(c64["params"]) == R.CHAIN_EPOCHS and rows.shape == (R.CHAIN_EPOCHS, case.batch)
+    for i, k in enumerate(R.PPO_TENSORS):
+        want, w0 = c64["params"][-1][i], d["cur"][i]
+        assert np.isfinite(want).all()
+        limit = R.chain_limit(err_t[k], want, w0, R.CHAIN_EPOCHS)
+        far = R.chain_err(stale["params"][-1][i], want, w0)
+        print("chain %-34s %-3s err_t %.3e limit %.3e (floor %.3e) stale %.3e = %.0f limits" % (
+            R.case_id(case), k, err_t[k], limit, R.chain_limit(0.0, want, w0, R.CHAIN_EPOCHS), far, far / limit))
+        assert far >= R.CHAIN_STALE_FACTOR * limit, (k, far, limit)
+    assert set(R.TRUNK_TENSORS) <= set(R.PPO_TENSORS)
+    for k, e in err_t.items():
+        if " " in k:  # "policy_loss 2": a statistic of an epoch
+            assert np.isfinite(e) and 8.0 * e <= R.CAP, (k, e)
+    assert (stale["params"][0][0] == c64["params"][0][0]).all()  # epoch 0 has nothing stale to read
+
+
+def test_ppo_ragged_inputs_give_the_stated_length_patterns():
+    case = R.CHAIN_CASES[1]
+    lengths = R.ragged_lengths(R.N_ENVS)
+    assert set(lengths.tolist()) == {0, 1, 2, 5} and all((lengths == v).sum() == R.N_ENVS // 4 for v in (0, 1, 2, 5))
+    assert set(R.ragged_lengths(16).tolist()) == {0, 1, 2, 5} and (R.ragged_lengths(48)[16:32] == R.ragged_lengths(16)).all()  # per member
+    d = R.ppo_ragged_inputs(case, R.RAGGED_HORIZON, lengths)
+    k0 = R.ENV_CELLS[case.env]
+    assert d["states"].shape == (5, 64, k0) and d["states"].dtype == np.int8 and d["actions"].shape == (5, 64) and d["actions"].dtype == np.uint8
+    assert d["returns"].shape == (64, 5) and d["returns"].dtype == np.float32 and d["lengths"].dtype == np.int32 and (d["lengths"] == lengths).all()
+    assert [p.shape for p in d["cur"]] == [(case.hidden, k0), (case.hidden,), (case.hidden, case.hidden), (case.hidden,), (4, case.hidden), (4,), (1, case.hidden), (1,)]
+    assert all(p.dtype == np.float32 and not np.array_equal(p, o) for p, o in zip(d["cur"], d["old"]))
+    sparse = R.sparse_lengths()
+    s = R.ppo_ragged_inputs(case, R.SPARSE_HORIZON, sparse)
+    assert sorted(sparse.tolist()) == [0] * 60 + [16] * 4 and s["actions"].shape == (16, 64)
+    valid = np.arange(R.SPARSE_HORIZON)[:, None] < sparse[None, :]
+    assert valid.sum() * 16 == valid.size  # exactly one (t, trajectory) candidate in 16 is valid
+    assert len({i // 16 for i in np.flatnonzero(sparse)}) == 4  # a full trajectory among every 16 columns
+    with pytest.raises(AssertionError):
+        R.ppo_ragged_inputs(case, 5, np.zeros(64, dtype=np.int32))  # (an all-zero rollout is no input of these tests)

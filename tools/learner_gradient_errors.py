@@ -3,7 +3,11 @@ coefficient, err_k (kernel against float64), err_t (torch-float32 against float6
 over its allowance for step B; the one-launch child against float64 and against the two-launch form. -> profiles/learner_gradients/errors.log
 With --cnn the same lines for the conv learner alone (tests/test_gpu_ppo_cnn_gradients.py: steps A and B of every case, the ragged
 rollout's statistics, whether the two-epoch call was bit-identical), then the median err_k / err_t over the gradient tensors and the
-figure closest to its limit -> profiles/ppo_cnn_gradients/errors.log. Without --cnn the MLP learners alone, line for line as before."""
+figure closest to its limit -> profiles/ppo_cnn_gradients/errors.log. With --chain what tests/test_gpu_ppo_epoch_chain.py measures alone:
+the torch-float32 chain's err_t and the stale-epoch emulation's distance per tensor (the CPU side), then per chain case err_k, the limit
+and err_k / err_t of the eight tensors and of every epoch's statistics, and for every run of its parts (a) and (b) whether the epochs in one
+call left the bytes of the calls of one epoch -> profiles/ppo_epoch_chain/errors.log. Without either flag the MLP learners alone, line for
+line as before."""
 import os
 import sys
 import tempfile
@@ -16,7 +20,8 @@ import learner_reference as R  # noqa: E402
 import test_gpu_learner_gradients as T  # noqa: E402
 
 CNN = "--cnn" in sys.argv
-MLP = not CNN
+CHAIN = "--chain" in sys.argv
+MLP = not CNN and not CHAIN
 
 worst = [0.0, ""]  # the largest err_k / err_t and where
 closest = [0.0, ""]  # the largest measured / limit and where
@@ -46,6 +51,15 @@ for c in R.PPO_CASES if MLP else ():
     print("yardstick ppo %-54s err_t " % R.case_id(c) + " ".join("%s %.2e" % kv for kv in R.ppo_yardstick(c)[2].items()))
 for c in R.PPO_CNN_CASES if CNN else ():
     print("yardstick ppo-cnn %-50s err_t " % R.cnn_case_id(c) + " ".join("%s %.2e" % kv for kv in R.ppo_cnn_yardstick(c)[2].items()))
+for c in R.CHAIN_CASES if CHAIN else ():
+    d, rows, state, c64, err_t = R.chain_yardstick(c)
+    stale = R.ppo_chain64(d, rows, state, R.CHAIN_STEP0, stale=True)
+    for i, k in enumerate(R.PPO_TENSORS):
+        want, w0 = c64["params"][-1][i], d["cur"][i]
+        limit, far = R.chain_limit(err_t[k], want, w0, R.CHAIN_EPOCHS), R.chain_err(stale["params"][-1][i], want, w0)
+        print("yardstick chain %-36s %-3s moved %.3e  err_t %.3e  limit %.3e  stale epochs %.3e = %.0f limits" % (
+            R.case_id(c), k, float(np.abs(want - w0).max()), err_t[k], limit, far, far / limit))
+    print("yardstick chain %-36s err_t " % R.case_id(c) + " ".join("%s %.2e" % kv for kv in err_t.items() if " " in kv[0]))
 if "--cpu" in sys.argv:
     sys.exit(0)
 
@@ -94,8 +108,32 @@ def cnn_learner():
         show("ppo-cnn ragged " + R.cnn_case_id(c), TC.ragged_figures(c, res["ragged"][0]))
 
 
+def epoch_chain():
+    import test_gpu_ppo_epoch_chain as TE
+
+    same = []
+    for run in TE.RUNS + TE.CHAIN_RUNS:
+        out = TE.single_result(run)[0]
+        bad, again = TE._bytes_differ(out["one"], out["chain"]), TE._bytes_differ(out["one"], out["again"])
+        same.append(not bad and not again)
+        print("epochs in one call vs calls of one epoch %-56s bit-identical: %s%s; the one call twice: %s" % (
+            TE.run_id(run), not bad, "" if not bad else " (differs in " + " ".join(bad) + ")", not again), flush=True)
+    for run in TE.MEMBER_RUNS:
+        out = TE.members_result(run)[0]
+        bad, again = TE._bytes_differ(out["one"], out["chain"]), TE._bytes_differ(out["one"], out["again"])
+        same.append(not bad and not again)
+        print("members: epochs in one launch vs launches of one epoch %-42s bit-identical: %s%s; the one launch twice: %s" % (
+            TE.run_id(run), not bad, "" if not bad else " (differs in " + " ".join(bad) + ")", not again), flush=True)
+    print("bit-identical: %d of %d runs" % (sum(same), len(same)))
+    for c, run in zip(R.CHAIN_CASES, TE.CHAIN_RUNS):
+        show("chain " + R.case_id(c), TE.chain_figures(c, TE.single_result(run)[0]["one"]))
+
+
 if MLP:
     mlp_learners()
+if CHAIN:
+    epoch_chain()
+    print("closest to its limit: %.3f of it at %s" % tuple(closest))
 if CNN:
     cnn_learner()
 if CNN:
