@@ -512,6 +512,36 @@ SGK_API int sgk_dqn_sgd_step(sgk_env *h, const sgk_dqn_learner *learner);
  * sgk_dqn_sgd_step followed by sgk_reset_done_store. */
 SGK_API int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *learner, uint32_t flags, int64_t slice, const int64_t *slice_dev,
                                          int32_t ring_slices, int8_t *states_ring);
+/* DeepQAgent.learn (reference value.py:113-136) for n_members INDEPENDENT DeepQAgents in one call: the same two launches as
+ * sgk_dqn_sgd_step with a member axis -- the SGD kernel's grid is one 1 024-lane workgroup per member, the Adam launch's
+ * n_members x ceil(P / 256) workgroups (workgroup -> (member, block)). Member m is the reference's `deep-q` run on the env columns
+ * m * E .. (m + 1) * E - 1, E = n_envs / n_members.
+ *   stacked tensors  every tensor of `learner` but the replay ring exists once per member, stacked on a leading member axis in one
+ *                    contiguous tensor, and the learner's pointers address member 0: w1 [n_members][H][n_cells], b1 [n_members][H],
+ *                    w2 [n_members][H][H], b2 [n_members][H], w3 [n_members][4][H], b3 [n_members][4]; w1t [n_members][n_cells][H],
+ *                    w2t [n_members][H][H], w3t [n_members][H][4]; m[i] / v[i] / vmax[i] like their parameter; the target's tw1t
+ *                    [n_members][n_cells][H], tb1, tw2t [n_members][H][H], tb2, tw3 [n_members][4][H], tb3 [n_members][4]; step int64
+ *                    [n_members]; loss_out float [n_members] or NULL; rows / rows_out int64 [n_members][batch] or NULL.
+ *   shared           the replay ring ([slices][n_envs][...], all members' env columns side by side, as sgk_step_store fills it) and
+ *                    every hyper-parameter.
+ *   rows             transitions keep their GLOBAL index slice * n_envs + env. Member m draws d uniformly from [0, slices_filled * E)
+ *                    with sgk_dqn_sgd_step's Philox call (stream 4, counter (sample, 0, its own Adam step, 4)) keyed by
+ *                    member_keys_dev[m] (uint64 [n_members], device; NULL: the handle's seed for every member) and trains on the
+ *                    transition (d / E) * n_envs + m * E + d % E; rows_out receives these global indices. A handle of E envs created at
+ *                    env_index_base + m * E draws the same transitions of its own ring with sgk_dqn_sgd_step.
+ *   a caller's row   that is outside the stored transitions, or whose env is not one of member m's own, trains on the member's first
+ *                    transition (slice 0, env m * E) -- not on wild memory, and not on another member's data.
+ *   workspace        device memory of sgk_dqn_members_workspace_bytes(h, n_hidden, n_members) bytes, 16-byte aligned, the CALLER's:
+ *                    member m's clip coefficient and flat gradient cross from the first launch to the second in its m-th slice. Its
+ *                    contents mean nothing between calls. No allocation, no host synchronisation, nothing of the handle's scratch block:
+ *                    the call can be recorded in a graph as the first call on a handle.
+ * n_members = 1 with member_keys_dev NULL IS sgk_dqn_sgd_step (the same kernels, the same bits). SGK_ERR_INVALID for n_members < 1,
+ * n_envs % n_members != 0, a NULL workspace, slices_filled * E >= 2^31 and whatever sgk_dqn_sgd_step refuses. A workgroup of the SGD
+ * kernel fills a CU's LDS: the members run one per CU, and in waves above one member per CU.
+ * sgk_dqn_members_workspace_bytes: -1 (and sgk_last_error) for a shape without a kernel. */
+SGK_API int64_t sgk_dqn_members_workspace_bytes(sgk_env *h, int32_t n_hidden, int32_t n_members);
+SGK_API int sgk_dqn_sgd_step_members(sgk_env *h, const sgk_dqn_learner *learner, int32_t n_members, const uint64_t *member_keys_dev,
+                                     void *workspace);
 
 /* ---- PPOBaseAgent.learn (reference policy_base.py:64-131) for PPOMLPAgent's default topology as ONE kernel ---------- */
 /* All `n_epochs` minibatch updates of one learn() call: per epoch `batch` rows drawn uniformly with replacement from the

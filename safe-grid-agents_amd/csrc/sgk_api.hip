@@ -948,7 +948,21 @@ struct DqnResetStore {  // sgk_dqn_sgd_step_reset_store's second half
   int8_t *states_ring;
 };
 
-static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnResetStore *rs) {
+struct DqnMembers {  // sgk_dqn_sgd_step_members' own arguments
+  int32_t n_members;
+  const uint64_t *keys;
+  void *workspace;
+};
+
+static bool dqn_shape_has_kernel(int n_cells, int n_hidden) {
+  switch (n_cells) {
+  case 25: case 30: case 36: case 48: case 49: case 56: case 63: break;
+  default: return false;
+  }
+  return n_hidden == 64 || n_hidden == 100;
+}
+
+static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnResetStore *rs, const DqnMembers *mem = nullptr) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
   const void *need[] = {L->states, L->successors, L->actions, L->rewards, L->terminals, L->w1, L->b1, L->w2, L->b2, L->w3, L->b3,
@@ -961,7 +975,18 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
     return fail(SGK_ERR_INVALID, "sgk_dqn_sgd_step needs n_hidden 64 or 100 (the reference default), 1 <= batch <= 64, slices_filled >= 1");
   if (L->loss_mode != SGK_DQN_LOSS_REFERENCE && L->loss_mode != SGK_DQN_LOSS_PER_SAMPLE)
     return fail(SGK_ERR_INVALID, "loss_mode must be SGK_DQN_LOSS_REFERENCE (0) or SGK_DQN_LOSS_PER_SAMPLE (1)");
-  if ((int64_t)L->slices_filled * h->sh.n > (int64_t)INT32_MAX)
+  if (mem) {
+    if (mem->n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)mem->n_members);
+    if (h->sh.n % mem->n_members != 0)
+      return fail(SGK_ERR_INVALID, "n_envs (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                  (long long)h->sh.n, (int)mem->n_members);
+    if (!mem->workspace)
+      return fail(SGK_ERR_INVALID, "workspace is NULL: sgk_dqn_sgd_step_members works in the caller's sgk_dqn_members_workspace_bytes()");
+    if (!dqn_shape_has_kernel(h->sh.n_cells, L->n_hidden))
+      return fail(SGK_ERR_INVALID, "no learner kernel for %d cells and %d hidden units", (int)h->sh.n_cells, (int)L->n_hidden);
+    if ((int64_t)L->slices_filled * (h->sh.n / mem->n_members) > (int64_t)INT32_MAX)
+      return fail(SGK_ERR_INVALID, "a member's minibatch is drawn with 32-bit indices: slices_filled * n_envs / n_members must stay below 2^31");
+  } else if ((int64_t)L->slices_filled * h->sh.n > (int64_t)INT32_MAX)
     return fail(SGK_ERR_INVALID, "the minibatch is drawn with 32-bit transition indices: slices_filled * n_envs must stay below 2^31");
   if (sgk::dqn_sgd_lds_bytes(h->sh.n_cells, L->n_hidden) > 160u * 1024u)
     return fail(SGK_ERR_INVALID, "this n_cells / n_hidden does not fit the 160 KB of LDS the kernel works in");
@@ -992,7 +1017,13 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
     d.rs_flags = rs->flags; d.rs_slice = rs->slice; d.rs_slice_dev = reinterpret_cast<const long long *>(rs->slice_dev);
     d.rs_ring = rs->ring_slices; d.rs_states_ring = rs->states_ring;
   }
-  if (!one_launch || d.multi_wg || rs) {
+  if (mem) {  // the two-launch form on the caller's workspace: no allocation, nothing of the handle's
+    d.multi_wg = 0;
+    d.n_members = mem->n_members;
+    d.member_keys = mem->keys;
+    d.scratch = mem->workspace;
+    d.scratch_stride = sgk::dqn_members_scratch_stride(h->sh.n_cells, L->n_hidden);
+  } else if (!one_launch || d.multi_wg || rs) {
     const size_t need = sgk::dqn_sgd_scratch_bytes(h->sh.n_cells, L->n_hidden);
     if (h->learn_scratch_bytes < need) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1027,6 +1058,22 @@ int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *L, uint32_t 
   if (slice < 0 || ring_slices < 0 || (slice_dev && ring_slices < 1)) return fail(SGK_ERR_INVALID, "bad slice / ring_slices");
   const DqnResetStore rs{flags, slice, slice_dev, ring_slices, states_ring};
   return dqn_sgd_step_impl(h, L, &rs);
+} SGK_CATCH_STATUS
+
+int64_t sgk_dqn_members_workspace_bytes(sgk_env *h, int32_t n_hidden, int32_t n_members) try {
+  if (!h) return (int64_t)fail(SGK_ERR_INVALID, "handle is NULL");
+  if (n_members < 1 || !dqn_shape_has_kernel(h->sh.n_cells, n_hidden)) {
+    fail(SGK_ERR_INVALID, "sgk_dqn_members_workspace_bytes needs n_members >= 1, n_hidden 64 or 100 and a board of 25, 30, 36, 48, 49, 56 or "
+                          "63 cells (this level: %d cells, n_hidden %d, n_members %d)", (int)h->sh.n_cells, (int)n_hidden, (int)n_members);
+    return -1;
+  }
+  return (int64_t)n_members * (int64_t)sgk::dqn_members_scratch_stride(h->sh.n_cells, n_hidden);
+} SGK_CATCH_VALUE(-1)
+
+int sgk_dqn_sgd_step_members(sgk_env *h, const sgk_dqn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                             void *workspace) try {
+  const DqnMembers mem{n_members, member_keys_dev, workspace};
+  return dqn_sgd_step_impl(h, L, nullptr, &mem);
 } SGK_CATCH_STATUS
 
 // sgk_ppo_epochs (one member, the handle's seed) and sgk_ppo_epochs_members: the same checks, the same kernel

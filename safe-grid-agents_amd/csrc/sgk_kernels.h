@@ -134,6 +134,12 @@ struct DqnLearner {
   const long long *rs_slice_dev = nullptr;
   int32_t rs_ring = 0;
   int8_t *rs_states_ring = nullptr;
+  // sgk_dqn_sgd_step_members: every tensor above but the replay ring stacked [n_members][...], the pointers address member 0; member m
+  // draws from the env columns m * n / n_members .. with member_keys[m] (null: the shard's seed); `scratch` is then the caller's
+  // workspace, n_members slices of scratch_stride bytes (dqn_members_scratch_stride)
+  int n_members = 1;
+  const uint64_t *member_keys = nullptr;
+  size_t scratch_stride = 0;
 };  // (the replay's int8 rewards are in units of the level's reward_scale: launch_dqn_sgd takes it from the shard's rules)
 // env.step + the second half of ReplayBuffer.add / reset_done + the first half for the next step, one launch each (sgk_step.hip)
 hipError_t launch_step_store(const Shard &sh, const uint8_t *actions, uint32_t flags, int cheat, int64_t slice, const long long *slice_dev,
@@ -145,6 +151,7 @@ hipError_t launch_replay_store(const Shard &sh, int phase, const uint8_t *action
                                hipStream_t st);
 size_t dqn_sgd_lds_bytes(int n_cells, int n_hidden);
 size_t dqn_sgd_scratch_bytes(int n_cells, int n_hidden);
+size_t dqn_members_scratch_stride(int n_cells, int n_hidden);
 hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st);
 struct PpoLearner {
   const int8_t *states;

@@ -14,6 +14,7 @@
 // every action equal, losses and weights within rtol 2e-4 (tests/test_gpu_batched_golden.py).
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "sgk_device.h"
 #include "sgk_step_store.h"
@@ -63,6 +64,10 @@ struct LearnArgs {
   float lr, beta1, beta2, eps, discount, max_norm;
   double reward_scale;  // what one unit of the int8 rewards is worth (SgkRules.reward_scale; 1 except tomato watering): the
                         // reference's reward is the float64 product, rounded to float32 when the batch tensor is made (value.py:170-171)
+  // sgk_dqn_sgd_step_members: one workgroup per member (see MemberOffsets); one member: member_envs = n_envs, member_total = total
+  int64_t member_envs, member_total;  // E = n_envs / n_members; the draw's range, filled slices * E
+  const uint64_t *member_keys;        // [n_members] Philox keys of the members' draws; null: `seed` for every member
+  int64_t scratch_stride;             // floats between two members' slices of adam_scratch
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -360,6 +365,22 @@ struct ParamMap {
   static constexpr int o_w1 = 0, o_b1 = H * K0, o_w2 = o_b1 + H, o_b2 = o_w2 + H * H, o_w3 = o_b2 + H, o_b3 = o_w3 + 4 * H, P = o_b3 + 4;
 };
 
+// The member axis (sgk_dqn_sgd_step_members; one member = sgk_dqn_sgd_step, offsets of zero): every tensor of LearnArgs but the replay
+// ring is stacked [n_members][...] and the pointers address member 0; a workgroup adds its member's offsets (wave-uniform address
+// arithmetic). The ring is shared: member m owns the env columns m * E ..
+// (m + 1) * E - 1 and draws from them alone. A workgroup of dqn_sgd_kernel fills a CU's LDS, so the members run one per CU and in
+// waves above that; dqn_adam_kernel's grid is n_members x ceil(P / 256), workgroup -> (member, block).
+template <int K0, int H>
+struct MemberOffsets {  // in elements, by tensor shape: W1 / W1^T, a hidden bias, W2 / W2^T, W3 / W3^T, b3 (32-bit: launch_dqn_sgd checks)
+  uint32_t mb;
+  __device__ __forceinline__ uint32_t w1() const { return mb * (uint32_t)(H * K0); }
+  __device__ __forceinline__ uint32_t b() const { return mb * (uint32_t)H; }
+  __device__ __forceinline__ uint32_t w2() const { return mb * (uint32_t)(H * H); }
+  __device__ __forceinline__ uint32_t w3() const { return mb * (uint32_t)(4 * H); }
+  __device__ __forceinline__ uint32_t b3() const { return mb * 4u; }
+  __device__ __forceinline__ uint32_t tensor(int ten) const { return ten == 0 ? w1() : ten == 2 ? w2() : ten == 4 ? w3() : ten == 5 ? b3() : b(); }
+};
+
 // Two launches instead of one (round 6): the SGD step's last phase -- Adam on 13.9 k parameters -- moves ~500 KB through ONE CU's
 // vector-memory path and took 10 of the kernel's 39 us (profiles/r06/dqn_timeline.log). With a.adam_scratch set, dqn_sgd_kernel stops
 // behind the norm: it stores the gradient (flat, torch's parameter order, 16 bytes per lane where the MFMA layout gives four
@@ -370,7 +391,9 @@ struct AdamHeader {
   float coef, lr_bc1, inv_bc2_sqrt, pad;
 };
 
-template <int K0, int H>
+// MEMBERS = false is the launch of one workgroup (sgk_dqn_sgd_step, and sgk_dqn_sgd_step_members with one member): the member index is
+// the constant 0 and every offset below folds away; MEMBERS = true is the same code with workgroup m serving member m.
+template <int K0, int H, bool MEMBERS = false>
 __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   SGK_STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char learn_smem[];
@@ -380,38 +403,56 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6, col = lane & 15, grp = lane >> 4;
   constexpr int MT = (H + 15) / 16, KT1 = (K0 + 15) / 16;  // 16-wide tiles along neurons / along board cells
+  // this member's slice of every stacked tensor: `a` stays as it came (kernel arguments, read where they are used) and the member's
+  // offsets are added at the uses (wave-uniform address arithmetic; a shifted copy of all 45 pointers would have to live in SGPRs)
+  const size_t mb = MEMBERS ? blockIdx.x : 0;
+  const MemberOffsets<K0, H> mo{(uint32_t)mb};
+  const long long env0 = MEMBERS ? (long long)mb * a.member_envs : 0;  // this member's first env column
+  const uint64_t seed = (MEMBERS && a.member_keys) ? a.member_keys[mb] : a.seed;
+  using TransitionId = typename std::conditional<MEMBERS, long long, int>::type;  // (one member: below 2^31, sgk_dqn_sgd_step checks)
 
   // ---- entry: ONE dependent chain of two memory round trips (the Adam step counter, then everything keyed by it) ----
   // minibatch: uniform with replacement over the stored transitions (contain.py:19-22), counter RNG. The index of the sample whose
   // bytes a lane fetches is derived by that lane (16 lanes per sample, each the same draw): the board gather needs no exchange
   // through LDS behind the draw, so indices, scalars and both boards travel together (they were two round trips and a barrier).
-  const long long step0 = *a.step;
+  const long long step0 = a.step[mb];
   // the first weight matrix and the small tensors are independent of it: requested first, so that they are in flight meanwhile
   RowsInFlight<H, K0> first;
-  rows_request<H, K0>(first, a.tw1t);
-  stage(L.w3, a.w3, 4 * H);
-  stage(L.tw3, a.tw3, 4 * H);
-  stage(L.b1, a.b1, H);
-  stage(L.b2, a.b2, H);
-  stage(L.tb1, a.tb1, H);
-  stage(L.tb2, a.tb2, H);
-  if (t < 4) { L.b3[t] = a.b3[t]; L.tb3[t] = a.tb3[t]; }
+  rows_request<H, K0>(first, a.tw1t + mo.w1());
+  stage(L.w3, a.w3 + mo.w3(), 4 * H);
+  stage(L.tw3, a.tw3 + mo.w3(), 4 * H);
+  stage(L.b1, a.b1 + mo.b(), H);
+  stage(L.b2, a.b2 + mo.b(), H);
+  stage(L.tb1, a.tb1 + mo.b(), H);
+  stage(L.tb2, a.tb2 + mo.b(), H);
+  if (t < 4) { L.b3[t] = a.b3[mo.b3() + t]; L.tb3[t] = a.tb3[mo.b3() + t]; }
   {
     const int b = t >> 4, kk = t & 15;  // sample, byte lane (64 samples x 16 lanes = the workgroup)
-    int id = 0;
+    // transitions are named by their GLOBAL index slice * n_envs + env; a member's draw `d` over its own filled slices * E transitions
+    // names (d / E) * n_envs + env0 + d % E (one member: E = n_envs, env0 = 0: d itself)
+    TransitionId id = (TransitionId)env0;
     if (b < B) {
       if (a.rows) {
-        const long long r = a.rows[b];
-        id = (r >= 0 && r < a.total) ? (int)r : 0;  // (an index outside the stored transitions reads transition 0, not wild memory)
+        // (an index outside the stored transitions, or of an env that is not the member's own, reads the member's first transition --
+        // slice 0, env env0: transition 0 with one member --, not wild memory)
+        const long long r = a.rows[mb * (size_t)a.batch + b];
+        if (r >= 0 && r < a.total) {
+          const long long e = MEMBERS ? r % a.n_envs - env0 : 0;
+          if (!MEMBERS || (e >= 0 && e < a.member_envs)) id = (TransitionId)r;
+        }
       } else {
         uint32_t x[4];
-        philox4x32_10((uint32_t)b, 0u, (uint32_t)step0, 4u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), x);
+        philox4x32_10((uint32_t)b, 0u, (uint32_t)step0, 4u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
         const unsigned long long r = ((unsigned long long)x[0] << 32) | x[1];
-        id = (int)__umul64hi(r, (unsigned long long)a.total);
+        const uint32_t d = (uint32_t)__umul64hi(r, (unsigned long long)(MEMBERS ? a.member_total : a.total));
+        if constexpr (MEMBERS) {
+          const uint32_t E = (uint32_t)a.member_envs, sl = d / E;
+          id = (long long)sl * a.n_envs + env0 + (d - sl * E);
+        } else id = (int)d;
       }
     }
     if (kk == 0) {
-      if (b < B && a.rows_out) a.rows_out[b] = id;
+      if (b < B && a.rows_out) a.rows_out[mb * (size_t)a.batch + b] = id;
       L.act[b] = a.actions[id] & 3;
       L.rew[b] = (float)((double)a.rewards[id] * a.reward_scale);
       L.term[b] = a.terminals[id] ? 1 : 0;
@@ -444,14 +485,14 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   // ---- target network on the successors; every next matrix is requested before the layer that precedes its use ----
   RowsInFlight<H, H> big;
   RowsInFlight<H, K0> small;
-  rows_request<H, H>(big, a.tw2t);
+  rows_request<H, H>(big, a.tw2t + mo.w2());
   dense_layer<K0, H, weight_stride(H)>(L.S2, KP, L.ST, L.tb1, L.C, true, nullptr);
   __syncthreads();
   SGK_STAMP(2);
   rows_commit<H, H>(L.ST, big);
   __syncthreads();
   SGK_STAMP(3);
-  rows_request<H, K0>(small, a.w1t);
+  rows_request<H, K0>(small, a.w1t + mo.w1());
   dense_layer<H, H, weight_stride(H)>(L.C, H, L.ST, L.tb2, L.D, true, nullptr);
   __syncthreads();
   SGK_STAMP(4);
@@ -460,14 +501,14 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   rows_commit<H, K0>(L.ST, small);
   __syncthreads();
   SGK_STAMP(5);
-  rows_request<H, H>(big, a.w2t);
+  rows_request<H, H>(big, a.w2t + mo.w2());
   dense_layer<K0, H, weight_stride(H)>(L.S, KP, L.ST, L.b1, L.A, true, nullptr);
   __syncthreads();
   SGK_STAMP(6);
   rows_commit<H, H>(L.ST, big);
   __syncthreads();
   SGK_STAMP(7);
-  rows_request<H, H>(big, a.w2);  // W2 as it is ([j][k]): the back-propagation through layer 2 wants it in this orientation
+  rows_request<H, H>(big, a.w2 + mo.w2());  // W2 as it is ([j][k]): the back-propagation through layer 2 wants it in this orientation
   dense_layer<H, H, weight_stride(H)>(L.A, H, L.ST, L.b2, L.Bq, true, nullptr);
   __syncthreads();
   SGK_STAMP(8);
@@ -601,30 +642,35 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   auto quad_ref = [&](int i) -> QuadRef {
     QuadRef r{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, false, 0};
     if (i == 0) {
-      if (own_w3) { const int k = 16 * wave + col; r = QuadRef{a.w3, a.m[4], a.v[4], a.vmax[4], a.w3t + 4 * k, k, H, 1, true, PM::o_w3}; }
-      else if (own_b3) r = QuadRef{a.b3, a.m[5], a.v[5], a.vmax[5], nullptr, 0, 1, 1, true, PM::o_b3};
+      if (own_w3) { const int k = 16 * wave + col; const uint32_t o = mo.w3(); r = QuadRef{a.w3 + o, a.m[4] + o, a.v[4] + o, a.vmax[4] + o, a.w3t + o + 4 * k, k, H, 1, true, PM::o_w3}; }
+      else if (own_b3) { const uint32_t o = mo.b3(); r = QuadRef{a.b3 + o, a.m[5] + o, a.v[5] + o, a.vmax[5] + o, nullptr, 0, 1, 1, true, PM::o_b3}; }
     } else if (i <= N2) {
       const int tile = wave + (i - 1) * (LWG / 64);
       if (tile < MT * MT) {
         const int j = 16 * (tile / MT) + col, k = 16 * (tile % MT) + 4 * grp;  // H % 4 == 0: the four columns k .. k + 3 are all inside
-        if (j < H && k < H) r = QuadRef{a.w2, a.m[2], a.v[2], a.vmax[2], a.w2t + (size_t)k * H + j, j * H + k, 1, H, true, PM::o_w2};
+        const uint32_t o = mo.w2();
+        if (j < H && k < H) r = QuadRef{a.w2 + o, a.m[2] + o, a.v[2] + o, a.vmax[2] + o, a.w2t + o + (size_t)k * H + j, j * H + k, 1, H, true, PM::o_w2};
       } else if (tile < T2) {
         const int jb = 16 * (tile - MT * MT) + 4 * grp;
-        if (col == 0 && jb < H) r = QuadRef{a.b2, a.m[3], a.v[3], a.vmax[3], nullptr, jb, 1, 1, true, PM::o_b2};
+        const uint32_t o = mo.b();
+        if (col == 0 && jb < H) r = QuadRef{a.b2 + o, a.m[3] + o, a.v[3] + o, a.vmax[3] + o, nullptr, jb, 1, 1, true, PM::o_b2};
       }
     } else {
       const int tile = wave + (i - 1 - N2) * (LWG / 64);
       if (tile < MT * KT1) {
         if (W1T) {
           const int j = 16 * (tile / KT1) + col, k = 16 * (tile % KT1) + 4 * grp;
-          if (j < H && k < K0) r = QuadRef{a.w1, a.m[0], a.v[0], a.vmax[0], a.w1t + (size_t)k * H + j, j * K0 + k, 1, H, true, PM::o_w1};
+          const uint32_t o = mo.w1();
+          if (j < H && k < K0) r = QuadRef{a.w1 + o, a.m[0] + o, a.v[0] + o, a.vmax[0] + o, a.w1t + o + (size_t)k * H + j, j * K0 + k, 1, H, true, PM::o_w1};
         } else {
           const int j = 16 * (tile / KT1) + 4 * grp, k = 16 * (tile % KT1) + col;
-          if (j < H && k < K0) r = QuadRef{a.w1, a.m[0], a.v[0], a.vmax[0], a.w1t + (size_t)k * H + j, j * K0 + k, K0, 1, true, PM::o_w1};
+          const uint32_t o = mo.w1();
+          if (j < H && k < K0) r = QuadRef{a.w1 + o, a.m[0] + o, a.v[0] + o, a.vmax[0] + o, a.w1t + o + (size_t)k * H + j, j * K0 + k, K0, 1, true, PM::o_w1};
         }
       } else if (tile < T1) {
         const int jb = 16 * (tile - MT * KT1) + 4 * grp;
-        if (col == 0 && jb < H) r = QuadRef{a.b1, a.m[1], a.v[1], a.vmax[1], nullptr, jb, 1, 1, true, PM::o_b1};
+        const uint32_t o = mo.b();
+        if (col == 0 && jb < H) r = QuadRef{a.b1 + o, a.m[1] + o, a.v[1] + o, a.vmax[1] + o, nullptr, jb, 1, 1, true, PM::o_b1};
       }
     }
     return r;
@@ -652,7 +698,8 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   // that rate. What would shorten it is more CUs, and a second workgroup costs a grid barrier: see the experiment below.)
   constexpr int QD = 2;
   if (a.adam_scratch) {  // (wave-uniform) two launches: the gradient leaves here, dqn_adam_kernel applies it
-    float *gout = a.adam_scratch + sizeof(AdamHeader) / sizeof(float);
+    float *const scratch = a.adam_scratch + mb * (size_t)a.scratch_stride;  // this member's slice of the workspace
+    float *gout = scratch + sizeof(AdamHeader) / sizeof(float);
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const QuadRef r = quad_ref(i);
@@ -672,9 +719,9 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
       hd.lr_bc1 = L.scratch[16];
       hd.inv_bc2_sqrt = L.scratch[17];
       hd.pad = 0.0f;
-      *reinterpret_cast<AdamHeader *>(a.adam_scratch) = hd;
-      *a.step = step0 + 1;
-      if (a.loss_out) *a.loss_out = loss;
+      *reinterpret_cast<AdamHeader *>(scratch) = hd;
+      a.step[mb] = step0 + 1;
+      if (a.loss_out) a.loss_out[mb] = loss;
     }
     SGK_STAMP(13);
     return;
@@ -726,8 +773,8 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
     }
   }
   if (t == 0) {
-    *a.step = step0 + 1;
-    if (a.loss_out) *a.loss_out = loss;
+    a.step[mb] = step0 + 1;
+    if (a.loss_out) a.loss_out[mb] = loss;
   }
 #ifdef SGK_LEARN_TIMELINE
 #ifdef SGK_LEARN_TIMELINE_ADAM
@@ -746,10 +793,12 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
 
 // Adam(amsgrad) + the transposed copies, one lane per parameter (the second launch of sgk_dqn_sgd_step: see AdamHeader above)
 template <int K0, int H>
-__device__ __forceinline__ void adam_body(const LearnArgs &a, int vblock) {
+__device__ __forceinline__ void adam_body(const LearnArgs &a, int vblock, size_t mb = 0) {
   using PM = ParamMap<K0, H>;
-  const AdamHeader hd = *reinterpret_cast<const AdamHeader *>(a.adam_scratch);
-  const float *g = a.adam_scratch + sizeof(AdamHeader) / sizeof(float);
+  const MemberOffsets<K0, H> mo{(uint32_t)mb};
+  const float *scratch = a.adam_scratch + mb * (size_t)a.scratch_stride;
+  const AdamHeader hd = *reinterpret_cast<const AdamHeader *>(scratch);
+  const float *g = scratch + sizeof(AdamHeader) / sizeof(float);
   AdamCoef ac;
   ac.lr_bc1 = hd.lr_bc1;
   ac.inv_bc2_sqrt = hd.inv_bc2_sqrt;
@@ -759,20 +808,23 @@ __device__ __forceinline__ void adam_body(const LearnArgs &a, int vblock) {
   const int ten = e < PM::o_b1 ? 0 : e < PM::o_w2 ? 1 : e < PM::o_b2 ? 2 : e < PM::o_w3 ? 3 : e < PM::o_b3 ? 4 : 5;
   const int off = ten == 0 ? PM::o_w1 : ten == 1 ? PM::o_b1 : ten == 2 ? PM::o_w2 : ten == 3 ? PM::o_b2 : ten == 4 ? PM::o_w3 : PM::o_b3;
   float *wp = ten == 0 ? a.w1 : ten == 1 ? a.b1 : ten == 2 ? a.w2 : ten == 3 ? a.b2 : ten == 4 ? a.w3 : a.b3;
-  const int le = e - off;
+  const size_t le = mo.tensor(ten) + (size_t)(e - off);  // (the member's slice of the tensor, then the element)
   float m = a.m[ten][le], v = a.v[ten][le], x = a.vmax[ten][le];
   const float nw = adam_scalar(wp[le], m, v, x, g[e] * hd.coef, ac);
   wp[le] = nw;
   a.m[ten][le] = m; a.v[ten][le] = v; a.vmax[ten][le] = x;
   // the transposed copies the policy kernels (W1^T, W3^T) and the next step's forward (W2^T) read
-  if (ten == 0) { const int j = le / K0, k = le - j * K0; a.w1t[(size_t)k * H + j] = nw; }
-  else if (ten == 2) { const int j = le / H, k = le - j * H; a.w2t[(size_t)k * H + j] = nw; }
-  else if (ten == 4) { const int ai = le / H, k = le - ai * H; a.w3t[4 * k + ai] = nw; }
+  const int l = e - off;
+  if (ten == 0) { const int j = l / K0, k = l - j * K0; a.w1t[mo.w1() + (size_t)k * H + j] = nw; }
+  else if (ten == 2) { const int j = l / H, k = l - j * H; a.w2t[mo.w2() + (size_t)k * H + j] = nw; }
+  else if (ten == 4) { const int ai = l / H, k = l - ai * H; a.w3t[mo.w3() + 4 * k + ai] = nw; }
 }
 
-template <int K0, int H>
+template <int K0, int H, bool MEMBERS = false>  // (MEMBERS as for dqn_sgd_kernel: false is the launch of one member's NB workgroups)
 __global__ __launch_bounds__(256) void dqn_adam_kernel(LearnArgs a) {
-  adam_body<K0, H>(a, (int)blockIdx.x);
+  constexpr int NB = (ParamMap<K0, H>::P + 255) / 256;  // the grid is n_members x NB: workgroup -> (member, block)
+  const int mb = MEMBERS ? (int)blockIdx.x / NB : 0;
+  adam_body<K0, H>(a, (int)blockIdx.x - mb * NB, (size_t)mb);
 }
 
 // Adam AND the lockstep step's last launch -- reset_done + the next transitions' states into the replay ring (sgk_reset_done_store) --
@@ -1703,6 +1755,12 @@ size_t dqn_sgd_scratch_bytes(int n_cells, int n_hidden) {
   return (need + 255) & ~(size_t)255;
 }
 
+// sgk_dqn_sgd_step_members' workspace (the caller's): one AdamHeader + flat gradient per member, at a 16-byte aligned stride
+size_t dqn_members_scratch_stride(int n_cells, int n_hidden) {
+  const size_t p = (size_t)n_hidden * n_cells + n_hidden + (size_t)n_hidden * n_hidden + n_hidden + 4 * (size_t)n_hidden + 4;
+  return (sizeof(AdamHeader) + sizeof(float) * p + 15) & ~(size_t)15;
+}
+
 #ifdef SGK_DQN_MULTI_WG
 // the four-workgroup form: LDS its workgroups need (0: no instantiation for this shape)
 template <int K0, int H>
@@ -1722,13 +1780,34 @@ static hipError_t launch_multi(const LearnArgs &a, void *scratch, int device, hi
 }
 #endif
 
+// the SGD kernel of one shape: the 160 KB dynamic-LDS opt-in is per kernel instantiation and device, made on its first launch there
+template <int K0, int H, bool MEMBERS>
+static hipError_t launch_sgd(const LearnArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
+  static std::atomic<unsigned long long> opted_in{0};
+  if (!((opted_in.load() >> (device & 63)) & 1ull)) {
+    hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&dqn_sgd_kernel<K0, H, MEMBERS>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (ae != hipSuccess) return ae;
+    opted_in.fetch_or(1ull << (device & 63));
+  }
+  dqn_sgd_kernel<K0, H, MEMBERS><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
+  return hipSuccess;
+}
+
 hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) {
   (void)hipGetLastError();
   if (L.n_hidden > 128 || L.n_hidden < 4 || (L.n_hidden & 3) || L.batch < 1 || L.batch > LB || sh.n_cells > 64) return hipErrorInvalidValue;
   if ((L.n_hidden / 4) * (L.n_hidden / 4) + L.n_hidden > LWG) return hipErrorInvalidValue;  // tile lanes + bias lanes
   const size_t lds = dqn_sgd_lds_bytes(sh.n_cells, L.n_hidden);
   if (lds > 160u * 1024u) return hipErrorInvalidValue;
+  const int n_members = L.n_members;
+  if (n_members < 1 || sh.n % n_members != 0) return hipErrorInvalidValue;
+  // members: the two-launch form on the caller's workspace only (no experiment kernel, no fused reset)
+  if (n_members > 1 && (!L.scratch || L.multi_wg || L.reset_store)) return hipErrorInvalidValue;
+  if ((int64_t)n_members * L.n_hidden * std::max(L.n_hidden, sh.n_cells) > (int64_t)UINT32_MAX) return hipErrorInvalidValue;  // MemberOffsets
   LearnArgs a;
+  a.member_envs = sh.n / n_members; a.member_total = (int64_t)L.slices_filled * a.member_envs;
+  a.member_keys = L.member_keys; a.scratch_stride = (int64_t)(L.scratch_stride / sizeof(float));
   a.states = L.states; a.successors = L.successors; a.actions = L.actions; a.rewards = L.rewards; a.terminals = L.terminals;
   a.n_envs = sh.n; a.total = (int64_t)L.slices_filled * sh.n; a.n_cells = sh.n_cells;
   a.w1 = L.w1; a.b1 = L.b1; a.w2 = L.w2; a.b2 = L.b2; a.w3 = L.w3; a.b3 = L.b3;
@@ -1756,18 +1835,15 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
 #define SGK_SGD_LAUNCH(K0V, HV)                                                                                            \
   do {                                                                                                                     \
     SGK_SGD_TRY_MULTI(K0V, HV);                                                                                            \
-    static std::atomic<unsigned long long> opted_in{0};                                                                                \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                        \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&dqn_sgd_kernel<K0V, HV>),                        \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
-    dqn_sgd_kernel<K0V, HV><<<dim3(1), dim3(LWG), lds, st>>>(a);                                                           \
+    hipError_t se = (n_members > 1 || a.member_keys) ? launch_sgd<K0V, HV, true>(a, n_members, lds, sh.device, st)         \
+                                                     : launch_sgd<K0V, HV, false>(a, 1, lds, sh.device, st);               \
+    if (se != hipSuccess) return se;                                                                                       \
     if (a.adam_scratch && !L.reset_store) {                                                                                \
       hipError_t le = hipGetLastError();                                                                                   \
       if (le != hipSuccess) return le;                                                                                     \
-      dqn_adam_kernel<K0V, HV><<<dim3((ParamMap<K0V, HV>::P + 255) / 256), dim3(256), 0, st>>>(a);                         \
+      const dim3 ag(n_members * ((ParamMap<K0V, HV>::P + 255) / 256));                                                     \
+      if (n_members > 1) dqn_adam_kernel<K0V, HV, true><<<ag, dim3(256), 0, st>>>(a);                                      \
+      else dqn_adam_kernel<K0V, HV, false><<<ag, dim3(256), 0, st>>>(a);                                                   \
     }                                                                                                                      \
   } while (0)
 #define SGK_SGD_LAUNCH_K(K0V)                                                                                              \

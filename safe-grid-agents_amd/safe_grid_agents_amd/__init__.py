@@ -8,6 +8,7 @@ from .agents import (AGENT_MAP, BatchedTabularQAgent, DeepQAgent, Experience, Ex
 from .ppo import BatchedPPOAgent, PPOBaseAgent, PPOCNNAgent, PPOMLPAgent, discounted_returns_f32
 from .ppo_population import BatchedPPOPopulation, default_member_seed, stack_state_dicts, unstack_state_dict
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
+from .deepq_population import BatchedDeepQPopulation
 from .envs import ENV_IDS, ENV_MAP, BatchedGridworldEnv, GridworldEnv, make
 from .loops import (EVAL_MAP, LEARN_MAP, WARMUP_MAP, BatchedRollout, batched_default_eval, batched_gather_rollout, batched_ppo_learn, batched_random_rollout, population_ppo_learn, batched_tabq_learn,
                     default_eval,
@@ -19,7 +20,7 @@ from .trainer import prepare_parser, train, train_batched
 __all__ = [
     "AGENT_MAP", "ENV_MAP", "ENV_IDS", "LEARN_MAP", "EVAL_MAP", "WARMUP_MAP",
     "make", "GridworldEnv", "BatchedGridworldEnv",
-    "RandomAgent", "SingleActionAgent", "TabularQAgent", "DeepQAgent", "BatchedTabularQAgent", "BatchedDeepQAgent", "DeviceReplay",
+    "RandomAgent", "SingleActionAgent", "TabularQAgent", "DeepQAgent", "BatchedTabularQAgent", "BatchedDeepQAgent", "BatchedDeepQPopulation", "DeviceReplay",
     "ReplayBuffer", "Experience", "ExperienceBatch", "Rollout",
     "BatchedPPOAgent", "batched_ppo_learn", "BatchedPPOPopulation", "population_ppo_learn", "default_member_seed", "stack_state_dicts",
     "unstack_state_dict", "PPOBaseAgent", "PPOMLPAgent", "PPOCNNAgent", "discounted_returns_f32",

@@ -26,7 +26,7 @@ def main(argv=None):
 
     args = prepare_parser().parse_args(argv)
     if getattr(args, "members", 0):
-        members_n_envs(args)  # --members M: N = M x rollouts
+        members_n_envs(args)  # --members M: ppo-mlp N = M x rollouts; deep-q -N a multiple of M
     if getattr(args, "devices", 1) > 1 and "WORLD_SIZE" not in os.environ:
         if getattr(args, "n_envs", 0) <= 0:
             raise SystemExit("--devices shards the batched trainer: give -N/--n-envs too")

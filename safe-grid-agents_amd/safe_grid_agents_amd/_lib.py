@@ -149,6 +149,8 @@ _SIGNATURES = {
     "sgk_policy_act": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_double, ctypes.c_uint64, _V, _V, _V, _V]),
     "sgk_dqn_sgd_step": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner)]),
     "sgk_dqn_sgd_step_reset_store": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner), ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
+    "sgk_dqn_members_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
+    "sgk_dqn_sgd_step_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner), ctypes.c_int32, _V, _V]),
     "sgk_convq_act": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_double, ctypes.c_uint64, _V, _V, _V, _V]),
     "sgk_convq_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_uint64, _V, _V, _V]),
     "sgk_convq_rollout": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.c_double, ctypes.c_uint64, ctypes.c_int32,

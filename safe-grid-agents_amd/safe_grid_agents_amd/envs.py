@@ -177,6 +177,7 @@ class BatchedGridworldEnv:
         self.observation_space = _Space(shape=(1, self.H, self.W))
         self._env = self  # track_metrics looks for env._env (reference meters.py:67-70)
         self._views = None
+        self._dqn_ws_bytes = {}  # (n_hidden, n_members) -> sgk_dqn_members_workspace_bytes, asked once
         self._finished_bufs = None
         self._tstream = None
         self._events = None
@@ -848,6 +849,31 @@ class BatchedGridworldEnv:
             kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
         self._sync_torch_to_lib()
         _lib.check(self.lib.sgk_ppo_epochs_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp))
+        self._sync_lib_to_torch()
+
+    def dqn_members_workspace_bytes(self, n_hidden, n_members):
+        """Bytes of device workspace sgk_dqn_sgd_step_members needs on this level for n_members members of n_hidden units; SgkError
+        for a shape without a kernel."""
+        nbytes = self.lib.sgk_dqn_members_workspace_bytes(self._h.ptr, int(n_hidden), int(n_members))
+        if nbytes < 0:
+            _lib.check(_lib.ERR_INVALID)
+        return int(nbytes)
+
+    def dqn_sgd_step_members(self, learner, n_members, member_keys=None, workspace=None):
+        """One DeepQAgent.learn() of n_members independent agents in two HIP launches (sgk_dqn_sgd_step_members); `learner` is a filled
+        _lib.SgkDqnLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None,
+        workspace a uint8 device tensor of dqn_members_workspace_bytes() bytes that the caller keeps alive."""
+        kp = wp = None
+        if member_keys is not None:
+            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
+        if workspace is not None:
+            key = (int(learner.n_hidden), int(n_members))
+            need = self._dqn_ws_bytes.get(key)
+            if need is None:
+                need = self._dqn_ws_bytes[key] = self.dqn_members_workspace_bytes(*key)
+            wp = ctypes.c_void_p(self._check(workspace, "workspace", numel=need, dtypes=("uint8",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_dqn_sgd_step_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp))
         self._sync_lib_to_torch()
 
     def ppo_cnn_epochs(self, learner):

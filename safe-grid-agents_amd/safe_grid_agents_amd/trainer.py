@@ -35,7 +35,8 @@ _CORE_FLAGS = [
     # under torch.distributed.run the launcher's WORLD_SIZE decides and this flag is only checked against it.
     ("devices", "G", dict(type=int, default=1)),
     # extension: with ppo-mlp, M independent agents (BatchedPPOPopulation) of `--rollouts` envs each in one batch of N = M x rollouts
-    # envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree.
+    # envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree. With deep-q, M independent agents
+    # (BatchedDeepQPopulation) of N / M envs each: the batch comes from -N, a multiple of M.
     ("members", "M", dict(type=int, default=0)),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
@@ -53,6 +54,8 @@ _PPO_FLAGS = [_LR,
               ("critic-coeff", "cc", dict(type=float, default=1.0)),
               ("entropy-bonus", "eb", dict(type=float, default=0.01)),
               _LAYERS]
+# --members is also accepted behind the agent's own flags (`... deep-q -l 1e-3 --members 32`); absent there, the core flag's value stays
+_MEMBERS = ("members", "M", dict(type=int, default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -69,8 +72,9 @@ _AGENT_FLAGS = {
                # Q-body built like policy_cnn.py:17-81, through PyTorch-ROCm; no parity claim (BASELINE config 4 says "conv policy")
                ("q-body", "qb", dict(type=str, default="mlp", choices=("mlp", "cnn"),
                                      help="mlp: the reference's network (default, pinned); cnn: non-parity conv body, -N only")),
-               ("n-channels", "ch", dict(type=int, default=5))],
-    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG],
+               ("n-channels", "ch", dict(type=int, default=5)),
+               _MEMBERS],
+    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS],
     "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG],
 }
 
@@ -178,7 +182,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
     members = int(getattr(args, "members", 0) or 0)
     if members:
-        members_n_envs(args)  # N = M x rollouts
+        members_n_envs(args)  # ppo-mlp: N = M x rollouts; deep-q: -N, a multiple of M
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -204,6 +208,14 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     sdist.library_comm(env)  # (several ranks under nccl) the metrics all-reduce's RCCL communicator, before the first flush
     if args.agent_alias == "tabular-q":
         agent = BatchedTabularQAgent(env, args)
+    elif members and args.agent_alias == "deep-q":
+        from .deepq_population import BatchedDeepQPopulation
+
+        # the replay holds whole lockstep slices: as many as cover the reference's capacity per member, at least 2
+        slices = max(2, -(-int(args.replay_capacity) // (env.n_envs // members)))
+        agent = BatchedDeepQPopulation(env, args, members, replay_slices=slices)
+        agent.warmup(slices)  # dqn_warmup (warmup.py:8-23) of every member: random-action transitions fill the replay
+        env.reset()
     elif members:
         agent = BatchedPPOPopulation(env, args, members)
     elif args.agent_alias in ("ppo-mlp", "ppo-cnn"):
@@ -233,7 +245,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     history = {"writer": writer, "t": 0, "t_learn": 0}
     period = 0
     for episode in range(1, args.episodes + 1):
-        if members:  # every member's rollout + epochs: two launches; the aggregate meters and the spread over the members
+        if members and ppo:  # every member's rollout + epochs: two launches; the aggregate meters and the spread over the members
             per_member, bm = population_ppo_learn(agent, env, history, cheat=args.cheat)
             history["t"] += horizon
             for tag, name in (("Train/member_return", "returns"), ("Train/member_safety", "safeties")):
@@ -246,6 +258,8 @@ def train_batched(args, writer_factory=None, reporter=_noop):
             if agent is None:
                 env.step_random(horizon, auto_reset=True)
             elif deepq:
+                if members:
+                    agent.reset_member_metrics()
                 for _ in range(horizon):  # dqn_learn for every env: act_explore, step, replay add, one SGD step, epsilon, sync
                     agent.step(learn=True, cheat=args.cheat)
             else:
@@ -254,10 +268,15 @@ def train_batched(args, writer_factory=None, reporter=_noop):
                     agent.check_hash_overflow()  # hashed tables (tomato watering): a full table stops the run at THIS period
             bm = sdist.global_metrics(env)  # this shard's metrics, all-reduced over the ranks when there are several
         bm.write(writer, episode, prefix="Train/")
+        if members and deepq:  # the spread over the members, as the PPO population writes it
+            per_member = agent.member_batch_metrics()
+            for tag, name in (("Train/member_return", "returns"), ("Train/member_safety", "safeties")):
+                writer.add_histogram(tag, np.array([m.meter(name)["avg"] for m in per_member], dtype=np.float64), episode)
         if agent is not None and not ppo:
             writer.add_scalar("Train/epsilon", agent.epsilon, agent.t)
         if deepq and agent.last_loss is not None:
-            writer.add_scalar("Train/value_loss", float(agent.last_loss.reshape(-1)[0]), agent.t)
+            loss = agent.last_loss.mean() if members else agent.last_loss.reshape(-1)[0]  # (a population: the members' mean)
+            writer.add_scalar("Train/value_loss", float(loss), agent.t)
         reporter(hidden_reward=bm.meter("safeties")["avg"], obs_reward=bm.meter("returns")["avg"])
         # evaluation cadence exactly as the reference's loops decide it: whiler (tabular-q / deep-q, learn.py:21-22) evaluates
         # after the episodes with episode % eval_every == eval_every - 1; ppo_learn (learn.py:100) after those with
@@ -274,13 +293,21 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
 
 def members_n_envs(args):
-    """--members M: the batch is N = M x rollouts envs. Sets args.n_envs; an explicit -N that disagrees, or another agent than ppo-mlp,
-    stops the run with a message."""
+    """--members M. ppo-mlp: the batch is N = M x rollouts envs (sets args.n_envs; an explicit -N that disagrees stops the run). deep-q:
+    the batch is -N envs, N / M per member (N must be a multiple of M). Another agent stops the run with a message."""
     members = int(args.members)
     if members < 1:
         raise SystemExit("--members must be >= 1")
+    if args.agent_alias == "deep-q":
+        n = int(getattr(args, "n_envs", 0) or 0)
+        if n < 1 or n % members:
+            raise SystemExit("--members %d with deep-q splits the -N envs evenly: -N %d is %d x %d + %d (give -N a multiple of %d)"
+                             % (members, n, members, n // members, n % members, members))
+        if getattr(args, "q_body", "mlp") != "mlp":
+            raise SystemExit("--members runs a population of the reference's MLP deep-q agents, not --q-body %s" % args.q_body)
+        return n
     if args.agent_alias != "ppo-mlp":
-        raise SystemExit("--members runs a population of ppo-mlp agents, not %r" % (args.agent_alias,))
+        raise SystemExit("--members runs a population of ppo-mlp or deep-q agents, not %r" % (args.agent_alias,))
     n = members * int(args.rollouts)
     if int(getattr(args, "n_envs", 0) or 0) not in (0, n):
         raise SystemExit("--members %d with --rollouts %d is a batch of %d envs; -N %d disagrees (leave -N out)"
