@@ -390,30 +390,34 @@ def ppo_cnn_gather(d, rows):
     return d["states"][t, n].reshape((len(rows),) + d["shape"]), d["actions"][t, n], d["returns"][n, t]
 
 
+def cnn_trunk(x, w):
+    """PPOCNNAgent's trunk on boards x [B, 1, H, W]: relu(conv3x3(relu(conv3x3(x)))) + conv1x1(x); w = (w1, b1, w2, b2, wb, bb, ...)."""
+    F = torch.nn.functional
+    h = torch.relu(F.conv2d(x, w[0], w[1], padding=1))
+    return torch.relu(F.conv2d(h, w[2], w[3], padding=1)) + F.conv2d(x, w[4], w[5])
+
+
+def cnn_head(t, wc, bc, wl, bl):
+    """One head on the trunk t: linear(flatten(relu(conv3x3(t)))). Shared with tests/forward_reference.py's cnn_forward."""
+    return torch.relu(torch.nn.functional.conv2d(t, wc, bc, padding=1)).flatten(1) @ wl.t() + bl
+
+
 def ppo_cnn_epoch64(params, old_params, boards, actions, returns, clipping, critic_coeff, entropy_bonus, dtype=torch.float64):
     """One epoch of PPOCNNAgent (ppo.py: PPOCNNAgent.forward + PPOBaseAgent.surrogate_loss) on a minibatch of boards [B, H, W]: the three
     logged scalars, the gradients of the 14 tensors in CNN_TENSORS order, the ratios and the critic's values."""
-    F = torch.nn.functional
     T = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).to(dtype)  # noqa: E731
     p = [T(x).requires_grad_(True) for x in params]
     o = [T(x) for x in old_params]
     x, r = T(boards).unsqueeze(1), T(returns)
     a = torch.as_tensor(np.asarray(actions, dtype=np.int64)).unsqueeze(1)
 
-    def trunk(w):
-        h = torch.relu(F.conv2d(x, w[0], w[1], padding=1))
-        return torch.relu(F.conv2d(h, w[2], w[3], padding=1)) + F.conv2d(x, w[4], w[5])
-
-    def head(t, wc, bc, wl, bl):
-        return torch.relu(F.conv2d(t, wc, bc, padding=1)).flatten(1) @ wl.t() + bl
-
-    tr = trunk(p)
-    logp_all = torch.log_softmax(head(tr, *p[6:10]), dim=-1)
-    values = head(tr, *p[10:14]).reshape(-1)
+    tr = cnn_trunk(x, p)
+    logp_all = torch.log_softmax(cnn_head(tr, *p[6:10]), dim=-1)
+    values = cnn_head(tr, *p[10:14]).reshape(-1)
     advantage = r - values
     advantage = (advantage - advantage.mean()) / advantage.std()
     with torch.no_grad():
-        old_logp = torch.log_softmax(head(trunk(o), *o[6:10]), dim=-1).gather(1, a).squeeze(1)
+        old_logp = torch.log_softmax(cnn_head(cnn_trunk(x, o), *o[6:10]), dim=-1).gather(1, a).squeeze(1)
     ratio = torch.exp(logp_all.gather(1, a).squeeze(1) - old_logp)
     entropy = -(logp_all.exp() * logp_all).sum(-1).mean()
     value_loss = ((values - r) ** 2).mean()
