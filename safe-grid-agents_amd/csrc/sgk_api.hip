@@ -955,11 +955,7 @@ struct DqnMembers {  // sgk_dqn_sgd_step_members' own arguments
 };
 
 static bool dqn_shape_has_kernel(int n_cells, int n_hidden) {
-  switch (n_cells) {
-  case 25: case 30: case 36: case 48: case 49: case 56: case 63: break;
-  default: return false;
-  }
-  return n_hidden == 64 || n_hidden == 100;
+  return sgk::mlp_cells_have_kernel(n_cells) && (n_hidden == 64 || n_hidden == 100);
 }
 
 static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnResetStore *rs, const DqnMembers *mem = nullptr) {
@@ -1007,23 +1003,17 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
   // the one kernel (the A/B knob of profiles/r06).
   static const bool one_launch = [] { const char *v = getenv("SGK_DQN_ONE_LAUNCH"); return v && v[0] == '1' && v[1] == 0; }();
   d.scratch = nullptr;
-  d.multi_wg = 0;
-#ifdef SGK_DQN_MULTI_WG
-  static const bool four_workgroups = [] { const char *v = getenv("SGK_DQN_WORKGROUPS"); return v && v[0] == '4' && v[1] == 0; }();
-  d.multi_wg = four_workgroups ? 1 : 0;
-#endif
   if (rs) {
     d.reset_store = 1;
     d.rs_flags = rs->flags; d.rs_slice = rs->slice; d.rs_slice_dev = reinterpret_cast<const long long *>(rs->slice_dev);
     d.rs_ring = rs->ring_slices; d.rs_states_ring = rs->states_ring;
   }
   if (mem) {  // the two-launch form on the caller's workspace: no allocation, nothing of the handle's
-    d.multi_wg = 0;
     d.n_members = mem->n_members;
     d.member_keys = mem->keys;
     d.scratch = mem->workspace;
     d.scratch_stride = sgk::dqn_members_scratch_stride(h->sh.n_cells, L->n_hidden);
-  } else if (!one_launch || d.multi_wg || rs) {
+  } else if (!one_launch || rs) {
     const size_t need = sgk::dqn_sgd_scratch_bytes(h->sh.n_cells, L->n_hidden);
     if (h->learn_scratch_bytes < need) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1041,7 +1031,6 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
     d.scratch = h->learn_scratch;
   }
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps; d.discount = L->discount; d.max_grad_norm = L->max_grad_norm;
-  if (rs && d.multi_wg) return fail(SGK_ERR_INVALID, "the four-workgroup experiment has no fused reset");
   SGK_HIP(sgk::launch_dqn_sgd(h->sh, d, h->stream));
   return SGK_OK;
 }
@@ -1063,8 +1052,8 @@ int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *L, uint32_t 
 int64_t sgk_dqn_members_workspace_bytes(sgk_env *h, int32_t n_hidden, int32_t n_members) try {
   if (!h) return (int64_t)fail(SGK_ERR_INVALID, "handle is NULL");
   if (n_members < 1 || !dqn_shape_has_kernel(h->sh.n_cells, n_hidden)) {
-    fail(SGK_ERR_INVALID, "sgk_dqn_members_workspace_bytes needs n_members >= 1, n_hidden 64 or 100 and a board of 25, 30, 36, 48, 49, 56 or "
-                          "63 cells (this level: %d cells, n_hidden %d, n_members %d)", (int)h->sh.n_cells, (int)n_hidden, (int)n_members);
+    fail(SGK_ERR_INVALID, "sgk_dqn_members_workspace_bytes needs n_members >= 1, n_hidden 64 or 100 and a board size the MLP "
+                          "kernels are instantiated for (this level: %d cells, n_hidden %d, n_members %d)", (int)h->sh.n_cells, (int)n_hidden, (int)n_members);
     return -1;
   }
   return (int64_t)n_members * (int64_t)sgk::dqn_members_scratch_stride(h->sh.n_cells, n_hidden);

@@ -123,13 +123,8 @@ hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channe
     constexpr size_t lds = ConvQGeom<HV, WV, CV>::lds_bytes;                                                               \
     const int64_t n_pass = (sh.n + ConvQGeom<HV, WV, CV>::ENVS - 1) / ConvQGeom<HV, WV, CV>::ENVS;                                                               \
     static_assert(lds <= 160u * 1024u, "convq LDS plan");                                                                 \
-    static std::atomic<unsigned long long> opted_in{0};                                                                    \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                 \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&convq_act_kernel<HV, WV, CV>),                   \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
+    hipError_t ae = allow_dynamic_lds<convq_act_kernel<HV, WV, CV>>(sh.device, (int)lds);                                  \
+    if (ae != hipSuccess) return ae;                                                                                       \
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                                \
     const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
     convq_act_kernel<HV, WV, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(sh.boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, \

@@ -191,13 +191,8 @@ hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_ch
     if (ConvDims<E>::H != sh.rules_host.height || ConvDims<E>::W != sh.rules_host.width) return hipErrorInvalidValue;      \
     constexpr size_t lds = LD::bytes;                                                                                      \
     const int64_t n_pass = (sh.n + LD::G::ENVS - 1) / LD::G::ENVS;                                                         \
-    static std::atomic<unsigned long long> opted_in{0};                                                                    \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                 \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&convq_rollout_kernel<E, CV>),                    \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
+    hipError_t ae = allow_dynamic_lds<convq_rollout_kernel<E, CV>>(sh.device, (int)lds);                                   \
+    if (ae != hipSuccess) return ae;                                                                                       \
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_ROLLOUT_WAVES_FOR(CV), (160u * 1024u) / lds));         \
     const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
     convq_rollout_kernel<E, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(a, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl); \

@@ -18,6 +18,8 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "sgk_kernels.h"
 #include "sgk_transition.h"  // EnvState, the counter RNG, transition<ENV>, begin_episode<ENV>, env_actual_action<ENV>
 
@@ -631,6 +633,18 @@ __device__ __forceinline__ void load_episode_index(EnvState &s, const int32_t *_
 // ------------------------------------------------------------------------------------------------
 static int grid_for(int64_t n_tiles, int cap) { return (int)(n_tiles < cap ? (n_tiles < 1 ? 1 : n_tiles) : cap); }
 
+// A kernel that takes more than 64 KB of dynamic LDS has to opt in: once per kernel instantiation and device, on its first launch
+// there (one bit per device; no allocation, so a launch inside a stream capture is as any other). The caller returns an error
+// before it launches anything.
+template <auto Kernel>
+static hipError_t allow_dynamic_lds(int device, int bytes) {
+  static std::atomic<unsigned long long> opted_in{0};
+  if ((opted_in.load() >> (device & 63)) & 1ull) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) opted_in.fetch_or(1ull << (device & 63));
+  return e;
+}
+
 #define SGK_DISPATCH_ENV_LAYOUT(ENVID, LAYOUT, ...)                                                     \
   do {                                                                                                     \
     if ((LAYOUT) == SGK_LAYOUT_COMPACT) {                                                                  \
@@ -676,6 +690,22 @@ static int grid_for(int64_t n_tiles, int cap) { return (int)(n_tiles < cap ? (n_
     case SGK_FRIEND_FOE: { constexpr int E = SGK_FRIEND_FOE; __VA_ARGS__; } break; \
     default: { constexpr int E = SGK_SIDE_EFFECTS_SOKOBAN; __VA_ARGS__; } break;               \
     }                                                                                    \
+  } while (0)
+
+// The board sizes (cells) the MLP kernels are instantiated for -- policy forward, DQN and PPO learners; mlp_cells_have_kernel() is
+// this list. Binds K0; a size without a kernel returns hipErrorInvalidValue from the calling function.
+#define SGK_DISPATCH_CELLS(NCELLS, ...)                                \
+  do {                                                                 \
+    switch (NCELLS) {                                                  \
+    case 25: { constexpr int K0 = 25; __VA_ARGS__; } break;            \
+    case 30: { constexpr int K0 = 30; __VA_ARGS__; } break;            \
+    case 36: { constexpr int K0 = 36; __VA_ARGS__; } break;            \
+    case 48: { constexpr int K0 = 48; __VA_ARGS__; } break;            \
+    case 49: { constexpr int K0 = 49; __VA_ARGS__; } break;            \
+    case 56: { constexpr int K0 = 56; __VA_ARGS__; } break;            \
+    case 63: { constexpr int K0 = 63; __VA_ARGS__; } break;            \
+    default: return hipErrorInvalidValue;                              \
+    }                                                                  \
   } while (0)
 
 static inline StepArgs make_step_args(const Shard &sh, const uint8_t *actions, uint32_t flags) {

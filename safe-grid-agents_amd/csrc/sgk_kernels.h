@@ -124,7 +124,6 @@ struct DqnLearner {
   const long long *rows;  // caller's minibatch or null
   long long *rows_out;    // minibatch used, or null
   void *scratch;          // dqn_sgd_scratch_bytes() of device memory (zeroed once): Adam runs as a second, chip-wide launch; null: inside the one kernel
-  int multi_wg;           // (-DSGK_DQN_MULTI_WG experiment build only) run the four-workgroup kernel on `scratch`
   double lr, beta1, beta2, eps, discount, max_grad_norm;
   // sgk_dqn_sgd_step_reset_store: the Adam launch also resets the finished envs and stores the next transitions' states (what
   // launch_reset_done_store does), as extra workgroups of the same grid
@@ -149,6 +148,7 @@ hipError_t launch_reset_done_store(const Shard &sh, uint32_t flags, int64_t slic
 hipError_t launch_replay_store(const Shard &sh, int phase, const uint8_t *actions, int cheat, int64_t head, const long long *head_dev,
                                int8_t *states, int8_t *successors, uint8_t *r_actions, int8_t *r_rewards, uint8_t *r_terminals,
                                hipStream_t st);
+bool mlp_cells_have_kernel(int n_cells);  // the board sizes SGK_DISPATCH_CELLS (sgk_device.h) lists: MLP forward, DQN and PPO learners
 size_t dqn_sgd_lds_bytes(int n_cells, int n_hidden);
 size_t dqn_sgd_scratch_bytes(int n_cells, int n_hidden);
 size_t dqn_members_scratch_stride(int n_cells, int n_hidden);

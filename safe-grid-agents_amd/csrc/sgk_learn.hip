@@ -13,7 +13,6 @@
 // reference's own DeepQAgent runs (tests/golden/batched_dqn_*.npz, 320-330 steps across three target syncs) are reproduced with
 // every action equal, losses and weights within rtol 2e-4 (tests/test_gpu_batched_golden.py).
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 #include "sgk_device.h"
@@ -30,10 +29,8 @@ __device__ unsigned long long learn_stamps[32];
 // (stamps 30 / 31: the shader clock counter, s_memtime, at the first and at the latest stamp: in-kernel clock = their difference over
 // the wall-clock difference x 100 MHz)
 #define SGK_STAMP(i) do { if (threadIdx.x == 0) { learn_stamps[i] = wall_clock64(); learn_stamps[(i) == 0 ? 30 : 31] = __builtin_amdgcn_s_memtime(); } } while (0)
-#define SGK_MSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) { learn_stamps[i] = wall_clock64(); learn_stamps[(i) == 0 ? 30 : 31] = __builtin_amdgcn_s_memtime(); } } while (0)
 #else
 #define SGK_STAMP(i) do { } while (0)
-#define SGK_MSTAMP(i) do { } while (0)
 #endif
 
 constexpr int LWG = 1024;    // lanes of the one workgroup
@@ -386,7 +383,7 @@ struct MemberOffsets {  // in elements, by tensor shape: W1 / W1^T, a hidden bia
 // behind the norm: it stores the gradient (flat, torch's parameter order, 16 bytes per lane where the MFMA layout gives four
 // consecutive elements) and {clip coefficient, lr / bias_correction1, 1 / sqrt(bias_correction2)} to the handle's scratch block, and
 // dqn_adam_kernel -- one lane per parameter, every CU, coalesced -- applies the update behind the kernel boundary (a boundary costs
-// ~1.5 us; a grid barrier inside one launch 6-8: the experiment further down).
+// ~1.5 us; a grid barrier inside one launch 6-8: EXPERIMENTS R6.4).
 struct AdamHeader {
   float coef, lr_bc1, inv_bc2_sqrt, pad;
 };
@@ -695,7 +692,7 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   // spills -- so the trips are not what bounds it. With -DSGK_LEARN_TIMELINE_ADAM wave 0 takes 0.5-1.3 us per quad whatever the
   // distance and then waits 2.9 us at the barrier for the other waves: the phase moves ~500 KB (13.9 k parameters x 4 tensors in, 5
   // out, padded tiles and 4-lane bias quads at full instruction cost) through ONE CU's 64 B/clk vector-memory path at ~40 % of
-  // that rate. What would shorten it is more CUs, and a second workgroup costs a grid barrier: see the experiment below.)
+  // that rate. What would shorten it is more CUs, and a second workgroup costs a grid barrier: EXPERIMENTS R6.4.)
   constexpr int QD = 2;
   if (a.adam_scratch) {  // (wave-uniform) two launches: the gradient leaves here, dqn_adam_kernel applies it
     float *const scratch = a.adam_scratch + mb * (size_t)a.scratch_stride;  // this member's slice of the workspace
@@ -852,451 +849,6 @@ __global__ __launch_bounds__(256) void dqn_adam_reset_kernel(LearnArgs a, int ad
                                   (int)blockIdx.x - adam_blocks, (int)gridDim.x - adam_blocks);
   }
 }
-
-// ------------------------------------------------------------------------------------------------
-// EXPERIMENT (round 6; compiled only with -DSGK_DQN_MULTI_WG, never into the product library): the same SGD step on FOUR
-// workgroups. The idea: dqn_sgd_kernel above is one workgroup on one CU -- 21 us of its 40 in fp32 MFMA phases at 70 % of one CU's
-// matrix rate, 11 us in Adam through one CU's memory pipeline (profiles/r06/dqn_timeline_before.log) -- so give each of GW = 4
-// workgroups 16 of the 64 samples (one MFMA sample tile; with 16 samples' activations all four weight matrices fit LDS at once:
-// one batch of loads at entry, W2 held once with an odd row stride and read along either axis) and a quarter of Adam. What the
-// split costs is three grid-wide barriers: B1 the targets of all 64 samples (the reference's loss needs their MEAN in every
-// sample's gradient, value.py:119-123), B2 the four partial gradients (summed in the fixed order 0..3), B3 the partial norms.
-// MEASURED (profiles/r06/dqn_timeline_multi.log, MI355X, 2.39 GHz in-kernel): 58 us against the one-workgroup kernel's 41. The
-// barriers cost 6.8 / 8.3 / 6.1 us (agent-scope release + acquire: the XCDs' L2s are not coherent, a release writes an L2's dirty
-// lines back and everything read behind an acquire comes from HBM: the phases behind the barriers take 4.9 and 5.9 us for a few KB),
-// the entry 6.6 us (every workgroup's weights were last written by another XCD), and a layer of ONE tile per wave is
-// latency-bound (3.0 us: 25 dependent MFMAs behind four batches of LDS reads, nothing to overlap them with). Correct -- it passes
-// every DeepQ test, the reference-run fixtures included -- and slower; kept as the record of why the learner stays on one CU.
-// ------------------------------------------------------------------------------------------------
-#ifdef SGK_DQN_MULTI_WG
-constexpr int GW = 4;         // workgroups
-constexpr int NBW = LB / GW;  // samples per workgroup: one 16-wide MFMA tile
-
-struct LearnShared {  // in the scratch block the library keeps per env handle (zeroed when it is made)
-  unsigned int count, gen;
-  unsigned int pad[14];
-  float y[LB];         // every sample's TD target (B1)
-  float ss[GW];        // partial squared gradient norms (B3)
-  float loss[GW];      // partial loss sums (B2)
-  float pad2[8];
-};
-static_assert(sizeof(LearnShared) % 16 == 0, "the gradient partials behind it are read as dwords but keep it aligned");
-
-// every lane calls it; on return every global write made by any workgroup before its call is visible to every lane here
-__device__ __forceinline__ void grid_barrier(LearnShared *sh) {
-  __threadfence();  // release: this wave's stores are out of the CU and the XCD's L2 is written back (agent scope)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int g = __hip_atomic_load(&sh->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__hip_atomic_fetch_add(&sh->count, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(GW - 1)) {
-      __hip_atomic_store(&sh->count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sh->gen, g + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      while (__hip_atomic_load(&sh->gen, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == g) __builtin_amdgcn_s_sleep(1);
-    }
-  }
-  __syncthreads();
-  __threadfence();  // acquire: what this CU / XCD cached of the other workgroups' lines is dropped
-}
-
-// dense layer for ONE 16-sample tile: out[b][n] = epilogue(bias[n] + sum_k in[b][k] * wt(k, n)), wt(k, n) = w[k * RS + n * CS] (so a
-// matrix held once serves both orientations), on v_mfma_f32_16x16x4_f32 as dense_layer above; the MT neuron tiles go to the waves
-// wave_first .. wave_first + wave_count - 1 (two independent layers run side by side on disjoint wave sets).
-template <int K, int H, class T>
-__device__ __forceinline__ void dense16(const T *in, int KP, const float *w, int RS, int CS, const float *bias, float *out, bool relu,
-                                        const float *mask, int wave_first, int wave_count) {
-  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6) - wave_first;
-  if (wave < 0 || wave >= wave_count) return;
-  const int col = lane & 15, grp = lane >> 4;
-  constexpr int MT = (H + 15) / 16, KS = (K + 3) / 4;
-  constexpr int CH = KS < 8 ? KS : 8;
-  for (int tile = wave; tile < MT; tile += wave_count) {
-    const int n0 = 16 * tile;
-    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (bias && n0 + 4 * grp < H) acc = *reinterpret_cast<const f4 *>(bias + n0 + 4 * grp);
-    const T *xrow = in + col * KP;
-    const float *wcol = w + (n0 + col) * CS;  // (neuron rows >= H of the last tile read what lies behind the matrix, inside LDS, and are dropped)
-#pragma unroll
-    for (int c0 = 0; c0 < KS; c0 += CH) {
-      float av[CH], bv[CH];
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        const int k = 4 * (c0 + u) + grp;
-        if (4 * (c0 + u) + 3 < K) {
-          av[u] = wcol[k * RS];
-          bv[u] = load_x1(xrow, k);
-        } else if (4 * (c0 + u) < K) {
-          const int kc = k < K ? k : K - 1;
-          av[u] = k < K ? wcol[kc * RS] : 0.0f;
-          bv[u] = k < K ? load_x1(xrow, kc) : 0.0f;
-        } else {
-          av[u] = 0.0f;
-          bv[u] = 0.0f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < CH; ++u)
-        if (4 * (c0 + u) < K) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    }
-    const int n = n0 + 4 * grp;
-    if (n < H) {
-      if (relu) acc = __builtin_elementwise_max(acc, (f4){0.0f, 0.0f, 0.0f, 0.0f});
-      if (mask) {
-        const f4 m = *reinterpret_cast<const f4 *>(mask + col * H + n);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = m[c] > 0.0f ? acc[c] : 0.0f;
-      }
-      *reinterpret_cast<f4 *>(out + col * H + n) = acc;
-    }
-  }
-}
-
-// G[r][c] = sum over the 16 samples of d[b][row0 + r] * x[b][col0 + c] (one 16 x 16 tile of a weight gradient; C layout: lane
-// (col, grp), register r = G[4 grp + r][col]); ones = true: x = 1 (column sums: a bias gradient, the same in every column)
-template <class T>
-__device__ __forceinline__ f4 wgrad16(const float *d, int DS, int row0, const T *x, int XS, int col0, int lane, bool ones) {
-  const int col = lane & 15, grp = lane >> 4;
-  f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-  float av[NBW / 4], bv[NBW / 4];
-#pragma unroll
-  for (int s = 0; s < NBW / 4; ++s) {
-    av[s] = d[(4 * s + grp) * DS + row0 + col];
-    bv[s] = ones ? 1.0f : load_x1(x + (4 * s + grp) * XS, col0 + col);
-  }
-#pragma unroll
-  for (int s = 0; s < NBW / 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
-  return acc;
-}
-
-constexpr int w2_stride(int h) { return h | 1; }  // odd: a column walk (n along the lanes, stride w2_stride) and a row walk both spread over the banks
-
-struct MultiLds {
-  float *w2, *tw2t, *w1t, *tw1t, *w3, *tw3, *b1, *b2, *b3, *tb1, *tb2, *tb3, *A, *Bq, *C, *D, *q, *tq, *y, *scratch, *rew;
-  int8_t *S, *S2;
-  int *act, *term;
-};
-template <int K0, int H>
-__device__ __forceinline__ MultiLds carve_multi(unsigned char *base) {
-  constexpr int KP = (K0 + 3) & ~3, WS = weight_stride(H);
-  MultiLds L;
-  float *f = reinterpret_cast<float *>(base);
-  L.w2 = f; f += H * w2_stride(H) + 16;  // (+16: the partial last tile of a column walk reads up to 11 rows past the matrix; see dense16)
-  f = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(f) + 15) & ~(uintptr_t)15);
-  L.tw2t = f; f += H * WS;
-  L.w1t = f; f += K0 * WS;
-  L.tw1t = f; f += K0 * WS;
-  L.w3 = f; f += 4 * H;
-  L.tw3 = f; f += 4 * H;
-  L.b1 = f; f += H;
-  L.b2 = f; f += H;
-  L.tb1 = f; f += H;
-  L.tb2 = f; f += H;
-  L.b3 = f; f += 4;
-  L.tb3 = f; f += 4;
-  L.A = f; f += NBW * H;
-  L.Bq = f; f += NBW * H;
-  L.C = f; f += NBW * H;
-  L.D = f; f += NBW * H;
-  L.q = f; f += LB * 4;   // (LB, not NBW: wgrad16 on dq reads rows past the 16 samples' 4 values; they are dropped)
-  L.tq = f; f += NBW * 4;
-  L.y = f; f += LB;
-  L.scratch = f; f += 32;
-  L.rew = f; f += NBW;
-  L.act = reinterpret_cast<int *>(f); f += NBW;
-  L.term = reinterpret_cast<int *>(f); f += NBW;
-  L.S = reinterpret_cast<int8_t *>(f);
-  L.S2 = L.S + NBW * KP;
-  return L;
-}
-template <int K0, int H>
-constexpr size_t multi_lds_bytes() {
-  constexpr int KP = (K0 + 3) & ~3, WS = weight_stride(H);
-  return sizeof(float) * (size_t)(H * w2_stride(H) + 16 + 4 + H * WS + 2 * K0 * WS + 8 * H + 4 * H + 8 + 4 * NBW * H + LB * 4 + NBW * 4 + LB + 32 + 3 * NBW) +
-         2 * NBW * KP + 64;
-}
-
-template <int K0, int H>
-__global__ __launch_bounds__(LWG) void dqn_sgd_multi_kernel(LearnArgs a, LearnShared *sh, float *partials) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char learn_smem[];
-  using PM = ParamMap<K0, H>;
-  constexpr int KP = (K0 + 3) & ~3, WS = weight_stride(H), W2S = w2_stride(H);
-  constexpr int MT = (H + 15) / 16, KT1 = (K0 + 15) / 16;
-  const MultiLds L = carve_multi<K0, H>(learn_smem);
-  const int B = a.batch, t = threadIdx.x, wg = blockIdx.x;
-  const int lane = t & 63, wave = t >> 6, col = lane & 15, grp = lane >> 4;
-  SGK_MSTAMP(0);
-  const long long step0 = *a.step;  // (workgroup 0 bumps it after the last barrier: every workgroup has read it by then)
-
-  // ---- entry: ONE batch of loads. The minibatch index of the sample whose bytes a lane fetches is derived by that lane (16 lanes
-  // per sample): no exchange between the draw and the gather. Everything else -- four weight matrices, the small tensors -- is
-  // independent of it and travels at the same time.
-  {
-    const int bl = t >> 4, kk = t & 15;  // local sample (t < 256), byte lane
-    if (bl < NBW) {
-      const int b = wg * NBW + bl;       // sample of the minibatch
-      int id = 0;
-      if (b < B) {
-        if (a.rows) {
-          const long long r = a.rows[b];
-          id = (r >= 0 && r < a.total) ? (int)r : 0;
-        } else {
-          uint32_t x[4];
-          philox4x32_10((uint32_t)b, 0u, (uint32_t)step0, 4u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), x);
-          const unsigned long long r = ((unsigned long long)x[0] << 32) | x[1];
-          id = (int)__umul64hi(r, (unsigned long long)a.total);
-        }
-      }
-      if (kk == 0) {
-        if (b < B && a.rows_out) a.rows_out[b] = id;
-        L.act[bl] = a.actions[id] & 3;
-        L.rew[bl] = (float)((double)a.rewards[id] * a.reward_scale);
-        L.term[bl] = a.terminals[id] ? 1 : 0;
-      }
-#pragma unroll
-      for (int j = 0; j < (KP + 15) / 16; ++j) {
-        const int k = kk + 16 * j;
-        if (k < KP) {
-          const bool live = b < B && k < K0;
-          L.S[bl * KP + k] = live ? a.states[(int64_t)id * K0 + k] : (int8_t)0;
-          L.S2[bl * KP + k] = live ? a.successors[(int64_t)id * K0 + k] : (int8_t)0;
-        }
-      }
-    }
-  }
-  stage_rows<H>(L.tw1t, a.tw1t, K0);
-  stage_rows<H>(L.w1t, a.w1t, K0);
-  stage_rows<H>(L.tw2t, a.tw2t, H);
-  for (int i = t * 4; i < H * H; i += LWG * 4) {  // W2 as torch holds it, rows of W2S floats (odd: 4-byte pieces)
-    const f4 v = *reinterpret_cast<const f4 *>(a.w2 + i);
-    const int r = i / H, c = i - r * H;
-    float *d = L.w2 + r * W2S + c;
-    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-  }
-  stage(L.w3, a.w3, 4 * H);
-  stage(L.tw3, a.tw3, 4 * H);
-  stage(L.b1, a.b1, H);
-  stage(L.b2, a.b2, H);
-  stage(L.tb1, a.tb1, H);
-  stage(L.tb2, a.tb2, H);
-  if (t < 4) { L.b3[t] = a.b3[t]; L.tb3[t] = a.tb3[t]; }
-  if (t == LWG - 1) {  // Adam's bias corrections (two double-precision pow()) in the shadow of the loads
-    const long long step = step0 + 1;
-    L.scratch[16] = a.lr / (float)(1.0 - pow((double)a.beta1, (double)step));
-    L.scratch[17] = 1.0f / sqrtf((float)(1.0 - pow((double)a.beta2, (double)step)));
-  }
-  __syncthreads();
-  SGK_MSTAMP(1);
-  // ---- both networks forward, side by side: target on the successors (waves 0..7), Q on the states (waves 8..15) ----
-  dense16<K0, H>(L.S2, KP, L.tw1t, WS, 1, L.tb1, L.C, true, nullptr, 0, 8);
-  dense16<K0, H>(L.S, KP, L.w1t, WS, 1, L.b1, L.A, true, nullptr, 8, 8);
-  __syncthreads();
-  SGK_MSTAMP(2);
-  dense16<H, H>(L.C, H, L.tw2t, WS, 1, L.tb2, L.D, true, nullptr, 0, 8);
-  dense16<H, H>(L.A, H, L.w2, 1, W2S, L.b2, L.Bq, true, nullptr, 8, 8);  // wt(k, n) = W2[n][k]
-  __syncthreads();
-  SGK_MSTAMP(3);
-  if (t < NBW * 4) {  // heads: one lane per (sample, action), target and Q
-    const int b = t >> 2, ac = t & 3;
-    float st = L.tb3[ac], sq = L.b3[ac];
-    for (int k0 = 0; k0 < H; k0 += 4) {
-      const f4 wt_ = *reinterpret_cast<const f4 *>(L.tw3 + ac * H + k0), xt = *reinterpret_cast<const f4 *>(L.D + b * H + k0);
-      const f4 wq_ = *reinterpret_cast<const f4 *>(L.w3 + ac * H + k0), xq = *reinterpret_cast<const f4 *>(L.Bq + b * H + k0);
-      st = fmaf(xt[0], wt_[0], st); st = fmaf(xt[1], wt_[1], st); st = fmaf(xt[2], wt_[2], st); st = fmaf(xt[3], wt_[3], st);
-      sq = fmaf(xq[0], wq_[0], sq); sq = fmaf(xq[1], wq_[1], sq); sq = fmaf(xq[2], wq_[2], sq); sq = fmaf(xq[3], wq_[3], sq);
-    }
-    L.tq[t] = st;
-    L.q[t] = sq;
-  }
-  __syncthreads();
-  SGK_MSTAMP(4);
-  // ---- TD targets of this workgroup's samples; the reference's loss needs the mean over ALL of them (B1) ----
-  float target = 0.0f, qsa = 0.0f;
-  const int bg = wg * NBW + t;  // (meaningful for t < NBW)
-  if (t < NBW && bg < B) {
-    const float nq = fmaxf(fmaxf(L.tq[t * 4], L.tq[t * 4 + 1]), fmaxf(L.tq[t * 4 + 2], L.tq[t * 4 + 3]));
-    target = a.discount * (L.term[t] ? 0.0f : nq) + L.rew[t];
-    qsa = L.q[t * 4 + L.act[t]];
-  }
-  float ybar = 0.0f;
-  if (a.loss_mode == 0) {
-    if (t < NBW) sh->y[bg] = target;  // (0 for the padding samples b >= B)
-    grid_barrier(sh);
-  SGK_MSTAMP(5);
-    if (t < LB) L.y[t] = sh->y[t];
-    __syncthreads();
-    if (t < 64) {  // wave 0: the same sum, in the same order, in every workgroup
-      ybar = __ockl_wfred_add_f32(L.y[t]) / (float)B;
-    }
-    if (t == 0) L.scratch[18] = ybar;
-    __syncthreads();
-    ybar = L.scratch[18];
-  }
-  float sq = 0.0f;
-  if (t < NBW) {
-    float g = 0.0f;
-    if (bg < B) {
-      if (a.loss_mode == 0) {
-        const float d = qsa - ybar, e = target - ybar;
-        sq = fmaf(d, d, e * e);
-        g = 2.0f * d / (float)B;
-      } else {
-        const float d = qsa - target;
-        sq = d * d;
-        g = 2.0f * d / (float)B;
-      }
-    }
-    L.y[t] = g;
-  }
-  const float loss_part = block_sum(sq, L.scratch);  // (has barriers: y[] is visible afterwards)
-  if (t < NBW * 4) L.q[t] = ((t & 3) == L.act[t >> 2]) ? L.y[t >> 2] : 0.0f;  // q now holds dL/dq of the 16 samples
-  __syncthreads();
-  SGK_MSTAMP(6);
-  // ---- backward on this workgroup's 16 samples; the partial gradients go to scratch in torch's parameter order ----
-  float *mine = partials + (size_t)wg * PM::P;
-  dense16<4, H>(L.q, 4, L.w3, H, 1, nullptr, L.C, false, L.Bq, 0, 8);  // dL/dh2 = relu'(h2) * (dq W3)
-  if (wave >= 8 && wave - 8 < MT) {  // W3: columns k = 16 (wave - 8) .. of dq^T h2; the lanes of group 0 hold the four actions
-    const int k = 16 * (wave - 8) + col;
-    const f4 g = wgrad16(L.q, 4, 0, L.Bq, H, 16 * (wave - 8), lane, false);
-    if (grp == 0 && k < H) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mine[PM::o_w3 + r * H + k] = g[r];
-    }
-  } else if (wave == 8 + MT) {
-    const f4 g = wgrad16(L.q, 4, 0, L.Bq, H, 0, lane, true);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mine[PM::o_b3 + r] = g[r];
-    }
-  }
-  __syncthreads();
-  SGK_MSTAMP(7);
-  dense16<H, H>(L.C, H, L.w2, W2S, 1, nullptr, L.D, false, L.A, 0, 8);  // dL/dh1 = relu'(h1) * (dh2 W2): wt(k = j, n) = W2[j][n]
-  // meanwhile, on the other eight waves: W2 / b2 gradient tiles (they need dh2 = C and h1 = A only)
-  {
-    constexpr int T2 = MT * MT + MT;
-    for (int tile = wave - 8; wave >= 8 && tile < T2; tile += 8) {
-      if (tile < MT * MT) {
-        const int j0 = 16 * (tile / MT), k0 = 16 * (tile % MT);
-        const f4 g = wgrad16(L.C, H, j0, L.A, H, k0, lane, false);
-        const int j = j0 + 4 * grp, k = k0 + col;
-        if (k < H) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (j + r < H) mine[PM::o_w2 + (j + r) * H + k] = g[r];
-        }
-      } else {
-        const int j = 16 * (tile - MT * MT) + 4 * grp;
-        const f4 g = wgrad16(L.C, H, 16 * (tile - MT * MT), L.A, H, 0, lane, true);
-        if (col == 0) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (j + r < H) mine[PM::o_b2 + j + r] = g[r];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  SGK_MSTAMP(8);
-  {
-    constexpr int T1 = MT * KT1 + MT;
-    for (int tile = wave; tile < T1; tile += LWG / 64) {
-      if (tile < MT * KT1) {
-        const int j0 = 16 * (tile / KT1), k0 = 16 * (tile % KT1);
-        const f4 g = wgrad16(L.D, H, j0, L.S, KP, k0, lane, false);
-        const int j = j0 + 4 * grp, k = k0 + col;
-        if (k < K0) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (j + r < H) mine[PM::o_w1 + (j + r) * K0 + k] = g[r];
-        }
-      } else {
-        const int j = 16 * (tile - MT * KT1) + 4 * grp;
-        const f4 g = wgrad16(L.D, H, 16 * (tile - MT * KT1), L.S, KP, 0, lane, true);
-        if (col == 0) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (j + r < H) mine[PM::o_b1 + j + r] = g[r];
-        }
-      }
-    }
-  }
-  SGK_MSTAMP(9);
-  if (t == 0) sh->loss[wg] = loss_part;
-  grid_barrier(sh);  // B2
-  SGK_MSTAMP(10);
-  // ---- this workgroup's quarter of the flat parameter vector: the gradient (partials summed in the fixed order 0..3), its share
-  // of the squared norm; Adam's state for those elements is requested before the norm's barrier and used behind it ----
-  constexpr int NE = (PM::P + GW * LWG - 1) / (GW * LWG);
-  float g[NE], pw[NE], pm[NE], pv[NE], px[NE];
-  float ss = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    const int e = wg * LWG + t + i * (GW * LWG);
-    g[i] = 0.0f;
-    pw[i] = pm[i] = pv[i] = px[i] = 0.0f;
-    if (e < PM::P) {
-      float s_ = partials[e];
-#pragma unroll
-      for (int w = 1; w < GW; ++w) s_ += partials[(size_t)w * PM::P + e];
-      g[i] = s_;
-      ss = fmaf(s_, s_, ss);
-      const int ten = e < PM::o_b1 ? 0 : e < PM::o_w2 ? 1 : e < PM::o_b2 ? 2 : e < PM::o_w3 ? 3 : e < PM::o_b3 ? 4 : 5;
-      const int off = ten == 0 ? PM::o_w1 : ten == 1 ? PM::o_b1 : ten == 2 ? PM::o_w2 : ten == 3 ? PM::o_b2 : ten == 4 ? PM::o_w3 : PM::o_b3;
-      const float *wp = ten == 0 ? a.w1 : ten == 1 ? a.b1 : ten == 2 ? a.w2 : ten == 3 ? a.b2 : ten == 4 ? a.w3 : a.b3;
-      pw[i] = wp[e - off];
-      pm[i] = a.m[ten][e - off];
-      pv[i] = a.v[ten][e - off];
-      px[i] = a.vmax[ten][e - off];
-    }
-  }
-  const float ss_part = block_sum(ss, L.scratch);
-  SGK_MSTAMP(11);
-  if (t == 0) sh->ss[wg] = ss_part;
-  grid_barrier(sh);  // B3
-  SGK_MSTAMP(12);
-  float total = 0.0f;
-#pragma unroll
-  for (int w = 0; w < GW; ++w) total += sh->ss[w];
-  const float coef = fminf(a.max_norm / (sqrtf(total) + 1e-6f), 1.0f);
-  AdamCoef ac;
-  ac.lr_bc1 = L.scratch[16];
-  ac.inv_bc2_sqrt = L.scratch[17];
-  ac.beta1 = a.beta1; ac.beta2 = a.beta2; ac.eps = a.eps;
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    const int e = wg * LWG + t + i * (GW * LWG);
-    if (e < PM::P) {
-      const int ten = e < PM::o_b1 ? 0 : e < PM::o_w2 ? 1 : e < PM::o_b2 ? 2 : e < PM::o_w3 ? 3 : e < PM::o_b3 ? 4 : 5;
-      const int off = ten == 0 ? PM::o_w1 : ten == 1 ? PM::o_b1 : ten == 2 ? PM::o_w2 : ten == 3 ? PM::o_b2 : ten == 4 ? PM::o_w3 : PM::o_b3;
-      float *wp = ten == 0 ? a.w1 : ten == 1 ? a.b1 : ten == 2 ? a.w2 : ten == 3 ? a.b2 : ten == 4 ? a.w3 : a.b3;
-      const int le = e - off;
-      float m = pm[i], v = pv[i], x = px[i];
-      const float nw = adam_scalar(pw[i], m, v, x, g[i] * coef, ac);
-      wp[le] = nw;
-      a.m[ten][le] = m; a.v[ten][le] = v; a.vmax[ten][le] = x;
-      // the transposed copies the policy kernels (W1^T, W3^T) and the one-workgroup learner (W2^T) read
-      if (ten == 0) { const int j = le / K0, k = le - j * K0; a.w1t[(size_t)k * H + j] = nw; }
-      else if (ten == 2) { const int j = le / H, k = le - j * H; a.w2t[(size_t)k * H + j] = nw; }
-      else if (ten == 4) { const int ai = le / H, k = le - ai * H; a.w3t[4 * k + ai] = nw; }
-    }
-  }
-#ifdef SGK_LEARN_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  SGK_MSTAMP(13);
-#endif
-  if (wg == 0 && t == 0) {
-    *a.step = step0 + 1;
-    if (a.loss_out) {
-      float l = 0.0f;
-#pragma unroll
-      for (int w = 0; w < GW; ++w) l += sh->loss[w];
-      *a.loss_out = l / (float)B;
-    }
-  }
-}
-
-#endif  // SGK_DQN_MULTI_WG
 
 // ------------------------------------------------------------------------------------------------
 // PPOBaseAgent.learn (reference policy_base.py:64-131) for PPOMLPAgent's default topology, ALL epochs in one launch: per
@@ -1744,53 +1296,49 @@ size_t dqn_sgd_lds_bytes(int n_cells, int n_hidden) {
   return sizeof(float) * (4 * LB * h + h * (size_t)weight_stride((int)h) + 8 * h + 4 * h + 8 + 2 * LB * 4 + LB + 32 + LB + 3 * LB) + 2 * LB * kp + 64;
 }
 
-// the handle's scratch block: AdamHeader + the flat gradient (two-launch Adam); in the experiment build also the four-workgroup
-// kernel's barrier words and partial gradients, whichever is larger
+// the learner's parameters (ParamMap<n_cells, n_hidden>::P for the shapes with a kernel)
+constexpr size_t dqn_param_count(int n_cells, int n_hidden) {
+  return (size_t)n_hidden * n_cells + n_hidden + (size_t)n_hidden * n_hidden + n_hidden + 4 * (size_t)n_hidden + 4;
+}
+static_assert(dqn_param_count(36, 100) == ParamMap<36, 100>::P && dqn_param_count(63, 64) == ParamMap<63, 64>::P, "one parameter count");
+
+// the handle's scratch block: AdamHeader + the flat gradient (two-launch Adam)
 size_t dqn_sgd_scratch_bytes(int n_cells, int n_hidden) {
-  const size_t p = (size_t)n_hidden * n_cells + n_hidden + (size_t)n_hidden * n_hidden + n_hidden + 4 * (size_t)n_hidden + 4;
-  size_t need = sizeof(AdamHeader) + sizeof(float) * p;
-#ifdef SGK_DQN_MULTI_WG
-  need = std::max(need, sizeof(LearnShared) + sizeof(float) * GW * p);
-#endif
-  return (need + 255) & ~(size_t)255;
+  return (sizeof(AdamHeader) + sizeof(float) * dqn_param_count(n_cells, n_hidden) + 255) & ~(size_t)255;
 }
 
 // sgk_dqn_sgd_step_members' workspace (the caller's): one AdamHeader + flat gradient per member, at a 16-byte aligned stride
 size_t dqn_members_scratch_stride(int n_cells, int n_hidden) {
-  const size_t p = (size_t)n_hidden * n_cells + n_hidden + (size_t)n_hidden * n_hidden + n_hidden + 4 * (size_t)n_hidden + 4;
-  return (sizeof(AdamHeader) + sizeof(float) * p + 15) & ~(size_t)15;
+  return (sizeof(AdamHeader) + sizeof(float) * dqn_param_count(n_cells, n_hidden) + 15) & ~(size_t)15;
 }
 
-#ifdef SGK_DQN_MULTI_WG
-// the four-workgroup form: LDS its workgroups need (0: no instantiation for this shape)
-template <int K0, int H>
-static hipError_t launch_multi(const LearnArgs &a, void *scratch, int device, hipStream_t st) {
-  constexpr size_t lds = multi_lds_bytes<K0, H>();
-  static std::atomic<unsigned long long> opted_in{0};
-  if (!((opted_in.load() >> (device & 63)) & 1ull)) {
-    hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&dqn_sgd_multi_kernel<K0, H>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (ae != hipSuccess) return ae;
-    opted_in.fetch_or(1ull << (device & 63));
-  }
-  LearnShared *sh = reinterpret_cast<LearnShared *>(scratch);
-  float *partials = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(scratch) + sizeof(LearnShared));
-  dqn_sgd_multi_kernel<K0, H><<<dim3(GW), dim3(LWG), lds, st>>>(a, sh, partials);
-  return hipGetLastError();
+bool mlp_cells_have_kernel(int n_cells) {
+  const auto dispatch = [](int n) -> hipError_t { SGK_DISPATCH_CELLS(n, { (void)K0; return hipSuccess; }); };
+  return dispatch(n_cells) == hipSuccess;
 }
-#endif
 
-// the SGD kernel of one shape: the 160 KB dynamic-LDS opt-in is per kernel instantiation and device, made on its first launch there
+// the SGD kernel of one shape (the 160 KB dynamic-LDS opt-in is made on its first launch per device)
 template <int K0, int H, bool MEMBERS>
 static hipError_t launch_sgd(const LearnArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
-  static std::atomic<unsigned long long> opted_in{0};
-  if (!((opted_in.load() >> (device & 63)) & 1ull)) {
-    hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&dqn_sgd_kernel<K0, H, MEMBERS>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (ae != hipSuccess) return ae;
-    opted_in.fetch_or(1ull << (device & 63));
-  }
+  hipError_t ae = allow_dynamic_lds<dqn_sgd_kernel<K0, H, MEMBERS>>(device, 160 * 1024);
+  if (ae != hipSuccess) return ae;
   dqn_sgd_kernel<K0, H, MEMBERS><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
+  return hipSuccess;
+}
+
+// one shape's launches: the SGD kernel and, with `adam`, dqn_adam_kernel behind it (the two-launch form without a fused reset)
+template <int K0, int H>
+static hipError_t launch_sgd_adam(const LearnArgs &a, int n_members, bool adam, size_t lds, int device, hipStream_t st) {
+  hipError_t se = (n_members > 1 || a.member_keys) ? launch_sgd<K0, H, true>(a, n_members, lds, device, st)
+                                                   : launch_sgd<K0, H, false>(a, 1, lds, device, st);
+  if (se != hipSuccess) return se;
+  if (adam) {
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return le;
+    const dim3 ag(n_members * ((ParamMap<K0, H>::P + 255) / 256));
+    if (n_members > 1) dqn_adam_kernel<K0, H, true><<<ag, dim3(256), 0, st>>>(a);
+    else dqn_adam_kernel<K0, H, false><<<ag, dim3(256), 0, st>>>(a);
+  }
   return hipSuccess;
 }
 
@@ -1802,8 +1350,8 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
   if (lds > 160u * 1024u) return hipErrorInvalidValue;
   const int n_members = L.n_members;
   if (n_members < 1 || sh.n % n_members != 0) return hipErrorInvalidValue;
-  // members: the two-launch form on the caller's workspace only (no experiment kernel, no fused reset)
-  if (n_members > 1 && (!L.scratch || L.multi_wg || L.reset_store)) return hipErrorInvalidValue;
+  // members: the two-launch form on the caller's workspace only (no fused reset)
+  if (n_members > 1 && (!L.scratch || L.reset_store)) return hipErrorInvalidValue;
   if ((int64_t)n_members * L.n_hidden * std::max(L.n_hidden, sh.n_cells) > (int64_t)UINT32_MAX) return hipErrorInvalidValue;  // MemberOffsets
   LearnArgs a;
   a.member_envs = sh.n / n_members; a.member_total = (int64_t)L.slices_filled * a.member_envs;
@@ -1816,55 +1364,18 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
   a.tw1t = L.tw1t; a.tb1 = L.tb1; a.tw2t = L.tw2t; a.tb2 = L.tb2; a.tw3 = L.tw3; a.tb3 = L.tb3;
   a.step = L.step; a.loss_out = L.loss_out; a.n_hidden = L.n_hidden; a.batch = L.batch;
   a.loss_mode = L.loss_mode; a.rows = L.rows; a.rows_out = L.rows_out;
-  a.adam_scratch = (L.scratch && !L.multi_wg) ? reinterpret_cast<float *>(L.scratch) : nullptr;
+  a.adam_scratch = reinterpret_cast<float *>(L.scratch);
   a.reward_scale = sh.rules_host.reward_scale;
   a.seed = sh.seed;
   a.lr = (float)L.lr; a.beta1 = (float)L.beta1; a.beta2 = (float)L.beta2; a.eps = (float)L.eps; a.discount = (float)L.discount;
   a.max_norm = (float)L.max_grad_norm;
-#ifdef SGK_DQN_MULTI_WG
-  /* (a shape whose four matrices do not fit a CU's LDS at once -- 7 x 9 boards with 100 units -- keeps the one-workgroup kernel) */
-#define SGK_SGD_TRY_MULTI(K0V, HV)                                                                                         \
-  do {                                                                                                                     \
-    if constexpr (multi_lds_bytes<K0V, HV>() <= 160u * 1024u) {                                                            \
-      if (L.scratch && L.multi_wg) return launch_multi<K0V, HV>(a, L.scratch, sh.device, st);                             \
-    }                                                                                                                      \
-  } while (0)
-#else
-#define SGK_SGD_TRY_MULTI(K0V, HV) do { } while (0)
-#endif
-#define SGK_SGD_LAUNCH(K0V, HV)                                                                                            \
-  do {                                                                                                                     \
-    SGK_SGD_TRY_MULTI(K0V, HV);                                                                                            \
-    hipError_t se = (n_members > 1 || a.member_keys) ? launch_sgd<K0V, HV, true>(a, n_members, lds, sh.device, st)         \
-                                                     : launch_sgd<K0V, HV, false>(a, 1, lds, sh.device, st);               \
-    if (se != hipSuccess) return se;                                                                                       \
-    if (a.adam_scratch && !L.reset_store) {                                                                                \
-      hipError_t le = hipGetLastError();                                                                                   \
-      if (le != hipSuccess) return le;                                                                                     \
-      const dim3 ag(n_members * ((ParamMap<K0V, HV>::P + 255) / 256));                                                     \
-      if (n_members > 1) dqn_adam_kernel<K0V, HV, true><<<ag, dim3(256), 0, st>>>(a);                                      \
-      else dqn_adam_kernel<K0V, HV, false><<<ag, dim3(256), 0, st>>>(a);                                                   \
-    }                                                                                                                      \
-  } while (0)
-#define SGK_SGD_LAUNCH_K(K0V)                                                                                              \
-  do {                                                                                                                     \
-    if (L.n_hidden == 100) SGK_SGD_LAUNCH(K0V, 100);                                                                       \
-    else if (L.n_hidden == 64) SGK_SGD_LAUNCH(K0V, 64);                                                                    \
-    else return hipErrorInvalidValue;                                                                                      \
-  } while (0)
-  switch (sh.n_cells) {  // the shapes with an instantiation: the four levels x {64, 100} hidden units
-  case 25: SGK_SGD_LAUNCH_K(25); break;
-  case 30: SGK_SGD_LAUNCH_K(30); break;
-  case 36: SGK_SGD_LAUNCH_K(36); break;
-  case 48: SGK_SGD_LAUNCH_K(48); break;
-  case 49: SGK_SGD_LAUNCH_K(49); break;
-  case 56: SGK_SGD_LAUNCH_K(56); break;
-  case 63: SGK_SGD_LAUNCH_K(63); break;
-  default: return hipErrorInvalidValue;
-  }
-#undef SGK_SGD_LAUNCH_K
-#undef SGK_SGD_LAUNCH
-#undef SGK_SGD_TRY_MULTI
+  const bool adam = a.adam_scratch && !L.reset_store;
+  hipError_t se = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
+  SGK_DISPATCH_CELLS(sh.n_cells, {  // the shapes with an instantiation: the levels' board sizes x {64, 100} hidden units
+    if (L.n_hidden == 100) se = launch_sgd_adam<K0, 100>(a, n_members, adam, lds, sh.device, st);
+    else if (L.n_hidden == 64) se = launch_sgd_adam<K0, 64>(a, n_members, adam, lds, sh.device, st);
+  });
+  if (se != hipSuccess) return se;
   if (L.reset_store) {  // Adam + reset_done + the next transitions' states in ONE launch behind the SGD kernel
     if (!a.adam_scratch) return hipErrorInvalidValue;  // (the two-launch form only: the gradient must leave the SGD kernel)
     hipError_t le = hipGetLastError();
@@ -1900,6 +1411,14 @@ extern "C" __attribute__((visibility("default"))) int sgk_debug_learn_stamps(uns
 
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden) { return ppo_lds_bytes((n_cells + 3) & ~3, n_hidden); }
 
+template <int K0, int H>
+static hipError_t launch_ppo(const PpoArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
+  hipError_t ae = allow_dynamic_lds<ppo_epochs_kernel<K0, H>>(device, 160 * 1024);
+  if (ae != hipSuccess) return ae;
+  ppo_epochs_kernel<K0, H><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
+  return hipSuccess;
+}
+
 hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys) {
   (void)hipGetLastError();
   if (P.batch < 2 || P.batch > LB || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 || P.n_trajectories >= (1ll << 31))
@@ -1919,37 +1438,13 @@ hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t s
   a.batch = P.batch; a.n_epochs = P.n_epochs; a.seed = sh.seed;
   a.lr = (float)P.lr; a.beta1 = (float)P.beta1; a.beta2 = (float)P.beta2; a.eps = (float)P.eps;
   a.clipping = (float)P.clipping; a.critic_coeff = (float)P.critic_coeff; a.entropy_bonus = (float)P.entropy_bonus;
-#define SGK_PPO_LAUNCH(K0V, HV)                                                                                            \
-  do {                                                                                                                     \
-    static std::atomic<unsigned long long> opted_in{0};                                                                                \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                        \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&ppo_epochs_kernel<K0V, HV>),                     \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
-    ppo_epochs_kernel<K0V, HV><<<dim3(n_members), dim3(LWG), lds, st>>>(a);                                                \
-  } while (0)
-#define SGK_PPO_LAUNCH_K(K0V)                                                                                              \
-  do {                                                                                                                     \
-    if (P.n_hidden == 100) SGK_PPO_LAUNCH(K0V, 100);                                                                       \
-    else if (P.n_hidden == 64) SGK_PPO_LAUNCH(K0V, 64);                                                                    \
-    else return hipErrorInvalidValue;                                                                                      \
-  } while (0)
-  switch (sh.n_cells) {
-  case 25: SGK_PPO_LAUNCH_K(25); break;
-  case 30: SGK_PPO_LAUNCH_K(30); break;
-  case 36: SGK_PPO_LAUNCH_K(36); break;
-  case 48: SGK_PPO_LAUNCH_K(48); break;
-  case 49: SGK_PPO_LAUNCH_K(49); break;
-  case 56: SGK_PPO_LAUNCH_K(56); break;
-  case 63: SGK_PPO_LAUNCH_K(63); break;
-  default: return hipErrorInvalidValue;
-  }
-#undef SGK_PPO_LAUNCH_K
-#undef SGK_PPO_LAUNCH
+  hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
+  SGK_DISPATCH_CELLS(sh.n_cells, {
+    if (P.n_hidden == 100) le = launch_ppo<K0, 100>(a, n_members, lds, sh.device, st);
+    else if (P.n_hidden == 64) le = launch_ppo<K0, 64>(a, n_members, lds, sh.device, st);
+  });
+  if (le != hipSuccess) return le;
   return hipGetLastError();
 }
-
 
 }  // namespace sgk

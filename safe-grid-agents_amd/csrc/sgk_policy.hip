@@ -2,7 +2,6 @@
 // value.py:94-111; PPOBaseAgent.act_explore, policy_base.py:54-64), the fused MLP forward + draw on the matrix cores
 // (value.py:89-111,148-158; policy_mlp.py:17-43) and PPOBaseAgent.get_discounted_returns (policy_base.py:179-186).
 #include <algorithm>
-#include <atomic>
 
 #include "sgk_device.h"
 #include "sgk_draws.h"
@@ -529,54 +528,44 @@ hipError_t launch_eps_greedy(const Shard &sh, int mode, const float *scores, uin
   return hipGetLastError();
 }
 
+template <int K0, int HID, int MODE>
+static hipError_t launch_act(const Shard &sh, const PolicyWeights &w, uint8_t *actions, float *scores, double eps, uint64_t draw,
+                             const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
+  constexpr size_t lds = PolicyMfmaGeom<K0, HID>::lds_bytes;
+  hipError_t ae = allow_dynamic_lds<policy_mfma_kernel<K0, HID, MODE>>(sh.device, (int)lds);
+  if (ae != hipSuccess) return ae;
+  const int grid = grid_for((sh.n + PMFMA_ENVS - 1) / PMFMA_ENVS, sh.n_cus);
+  policy_mfma_kernel<K0, HID, MODE><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(sh.boards, sh.pitch, w.w1t, w.b1, w.w2, w.b2, w.w3t, w.b3, actions,
+                                                                            scores, sh.n, eps, sh.seed, sh.env_base, draw, eps_dev, draw_dev);
+  return hipSuccess;
+}
+
 hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, uint8_t *actions, float *scores, double eps,
                              uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
   (void)hipGetLastError();
-  int grid = grid_for((sh.n + PMFMA_ENVS - 1) / PMFMA_ENVS, sh.n_cus);
-#define SGK_POLICY_LAUNCH_M(K0, HID, MODE)                                                                                 \
-  do {                                                                                                                     \
-    constexpr size_t lds = PolicyMfmaGeom<K0, HID>::lds_bytes;                                                             \
-    static std::atomic<unsigned long long> opted_in{0}; /* > 64 KB of dynamic LDS needs the opt-in, once per kernel and device */      \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                        \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_mfma_kernel<K0, HID, MODE>),              \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
-    policy_mfma_kernel<K0, HID, MODE><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(sh.boards, sh.pitch, w.w1t, w.b1, w.w2, w.b2, \
-                                                                              w.w3t, w.b3, actions, scores, sh.n, eps,     \
-                                                                              sh.seed, sh.env_base, draw, eps_dev,         \
-                                                                              draw_dev);                                   \
-  } while (0)
-#define SGK_POLICY_LAUNCH_H(K0, HID)                                                                                       \
-  do {                                                                                                                     \
-    if (mode == 0) SGK_POLICY_LAUNCH_M(K0, HID, 0);                                                                        \
-    else SGK_POLICY_LAUNCH_M(K0, HID, 1);                                                                                  \
-  } while (0)
-  // hidden widths with an instantiation: the reference default (100) and the two common powers of two
-#define SGK_POLICY_LAUNCH(K0)                                                                                              \
-  do {                                                                                                                     \
-    switch (w.n_hidden) {                                                                                                  \
-    case 64: SGK_POLICY_LAUNCH_H(K0, 64); break;                                                                           \
-    case 100: SGK_POLICY_LAUNCH_H(K0, 100); break;                                                                         \
-    case 128: SGK_POLICY_LAUNCH_H(K0, 128); break;                                                                         \
-    default: return hipErrorInvalidValue;                                                                                  \
-    }                                                                                                                      \
-  } while (0)
-  switch (sh.n_cells) {
-  case 25: SGK_POLICY_LAUNCH(25); break;
-  case 30: SGK_POLICY_LAUNCH(30); break;
-  case 36: SGK_POLICY_LAUNCH(36); break;
-  case 48: SGK_POLICY_LAUNCH(48); break;
-  case 49: SGK_POLICY_LAUNCH(49); break;
-  case 56: SGK_POLICY_LAUNCH(56); break;
-  case 63: SGK_POLICY_LAUNCH(63); break;
-  default: return hipErrorInvalidValue;
-  }
+  hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
+#define SGK_POLICY_LAUNCH(HID)                                                                              \
+  (mode == 0 ? launch_act<K0, HID, 0>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st)              \
+             : launch_act<K0, HID, 1>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st))
+  SGK_DISPATCH_CELLS(sh.n_cells, {
+    switch (w.n_hidden) {  // hidden widths with an instantiation: the reference default (100) and the two common powers of two
+    case 64: le = SGK_POLICY_LAUNCH(64); break;
+    case 100: le = SGK_POLICY_LAUNCH(100); break;
+    case 128: le = SGK_POLICY_LAUNCH(128); break;
+    }
+  });
 #undef SGK_POLICY_LAUNCH
-#undef SGK_POLICY_LAUNCH_H
-#undef SGK_POLICY_LAUNCH_M
+  if (le != hipSuccess) return le;
   return hipGetLastError();
+}
+
+template <int E, int HID, int MODE>
+static hipError_t launch_rollout(const RolloutArgs &a, int grid, int device, hipStream_t st) {
+  constexpr size_t lds = policy_rollout_lds_bytes<E, HID>();
+  hipError_t ae = allow_dynamic_lds<policy_rollout_kernel<E, HID, MODE>>(device, (int)lds);
+  if (ae != hipSuccess) return ae;
+  policy_rollout_kernel<E, HID, MODE><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(a);
+  return hipSuccess;
 }
 
 hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights &w, double eps, uint64_t draw0, int32_t n_steps,
@@ -598,33 +587,18 @@ hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights 
   a.member_wgs = grid_for((a.member_envs + PMFMA_ENVS - 1) / PMFMA_ENVS, std::max(sh.n_cus / n_members, 1));
   a.member_metrics = reinterpret_cast<long long *>(member_metrics);
   const int grid = n_members * a.member_wgs;
-#define SGK_ROLLOUT_LAUNCH_M(E, HID, MODE)                                                                                 \
-  do {                                                                                                                     \
-    constexpr size_t lds = policy_rollout_lds_bytes<E, HID>();                                                             \
-    static std::atomic<unsigned long long> opted_in{0};                                                                                \
-    if (!((opted_in.load() >> (sh.device & 63)) & 1ull)) {                                                                        \
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_rollout_kernel<E, HID, MODE>),            \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-      if (ae != hipSuccess) return ae;                                                                                     \
-      opted_in.fetch_or(1ull << (sh.device & 63));                                                                         \
-    }                                                                                                                      \
-    policy_rollout_kernel<E, HID, MODE><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(a);                                       \
-  } while (0)
-#define SGK_ROLLOUT_LAUNCH_H(E, HID)                                                                                       \
-  do {                                                                                                                     \
-    if (mode == 0) SGK_ROLLOUT_LAUNCH_M(E, HID, 0);                                                                        \
-    else SGK_ROLLOUT_LAUNCH_M(E, HID, 1);                                                                                  \
-  } while (0)
+  hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
+#define SGK_ROLLOUT_LAUNCH(HID) \
+  (mode == 0 ? launch_rollout<E, HID, 0>(a, grid, sh.device, st) : launch_rollout<E, HID, 1>(a, grid, sh.device, st))
   SGK_DISPATCH_ENV(sh.env_id, {
     switch (w.n_hidden) {
-    case 64: SGK_ROLLOUT_LAUNCH_H(E, 64); break;
-    case 100: SGK_ROLLOUT_LAUNCH_H(E, 100); break;
-    case 128: SGK_ROLLOUT_LAUNCH_H(E, 128); break;
-    default: return hipErrorInvalidValue;
+    case 64: le = SGK_ROLLOUT_LAUNCH(64); break;
+    case 100: le = SGK_ROLLOUT_LAUNCH(100); break;
+    case 128: le = SGK_ROLLOUT_LAUNCH(128); break;
     }
   });
-#undef SGK_ROLLOUT_LAUNCH_H
-#undef SGK_ROLLOUT_LAUNCH_M
+#undef SGK_ROLLOUT_LAUNCH
+  if (le != hipSuccess) return le;
   return hipGetLastError();
 }
 

@@ -1212,7 +1212,7 @@ hipError_t launch_tabq_rollout(const Shard &sh, const TabqShard &tq, int64_t n_s
   for (int64_t done = 0; done < n_steps && err == hipSuccess;) {
     const int32_t chunk = (int32_t)std::min<int64_t>(n_steps - done, (int64_t)1 << 30);
     const int n_ent = sh.rules_host.n_live_slots * 4;
-    auto go = [&](auto kernel) {
+    auto go = [&](auto kernel) {  // (not allow_dynamic_lds: the LDS size is the level's, chosen at run time, so it is set per launch)
       err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (err == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, st, a, chunk);
     };

@@ -1,7 +1,6 @@
 """sgk_dqn_sgd_step (config 4's learner: Sokoban 36-100-100-4, batch 64, replay of 8 x 32 768 transitions), device time per call from HIP
 events over 300 back-to-back calls, and one lockstep step of dqn_learn with learning (graph replay, host clock). Default: the
-one-workgroup kernel + Adam as a second, chip-wide launch; SGK_DQN_ONE_LAUNCH=1: Adam inside the one kernel (rounds 1-5's form).
-(Against a -DSGK_DQN_MULTI_WG build -- SGK_LIB_PATH, tools/gpu_dqn_timeline.sh ... multi -- SGK_DQN_WORKGROUPS=4 picks the four-workgroup experiment.)"""
+one-workgroup kernel + Adam as a second, chip-wide launch; SGK_DQN_ONE_LAUNCH=1: Adam inside the one kernel (rounds 1-5's form)."""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "safe-grid-agents_amd")):
