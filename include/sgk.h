@@ -437,6 +437,20 @@ SGK_API int sgk_convq_sample(sgk_env *h, const sgk_convq_weights *w, uint64_t dr
  * boards are materialised at the end. */
 SGK_API int sgk_convq_rollout(sgk_env *h, const sgk_convq_weights *w, int32_t mode, double epsilon, uint64_t draw_index0, int32_t n_steps,
                               uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev);
+/* The same launch for n_members INDEPENDENT conv bodies: gather_rollout's inner loop of n_members PPOCNNAgents at once, as
+ * sgk_policy_rollout_members is for the MLP bodies. Member m acts in the envs m * E .. (m + 1) * E - 1, E = n_envs / n_members, with the
+ * m-th slice of each of the ten weight tensors stacked on a leading member axis (w1 [n_members][C][1][3][3], ..., wl [n_members][4][C *
+ * n_cells], bl [n_members][4]); `w`'s pointers address member 0. A workgroup serves ONE member for the whole launch and a pass of envs
+ * never straddles two members; any number of members works (the grid is n_members x a member's workgroups). Env indices -- RNG keys
+ * (global env index), trajectory outputs [n_steps][n_envs][...], episode arrays -- are the handle's own, so member m's outputs are
+ * those of a handle of E envs created at env_index_base + m * E running sgk_convq_rollout with member m's weights, bit for bit.
+ * member_metrics_dev: int64 [n_members][SGK_METRICS_LEN] or NULL, the contract of sgk_policy_rollout_members (sums added, maxima
+ * raised: initialise the maxima to INT64_MIN). The member instantiation of the kernel is used for every n_members, 1 included (where
+ * it leaves the bytes sgk_convq_rollout leaves). SGK_ERR_INVALID for n_members < 1, n_envs % n_members != 0 and whatever
+ * sgk_convq_rollout refuses. */
+SGK_API int sgk_convq_rollout_members(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                                      uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev,
+                                      uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev);
 
 /* The two halves of the replay add FUSED into the launches around them (round 6; a lockstep step of dqn_learn -- learn.py:29-58 -- is
  * then sgk_policy_act, sgk_step_store, sgk_dqn_sgd_step, sgk_reset_done_store: four calls instead of six -- or three, with the last two
@@ -636,6 +650,26 @@ SGK_API int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *learner);
 /* The workspace sgk_ppo_cnn_epochs needs on this handle's level, in bytes; -1 (sgk_last_error says why) for an unsupported n_channels,
  * board shape or batch. */
 SGK_API int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch);
+/* sgk_ppo_cnn_epochs for n_members INDEPENDENT PPOCNNAgents: the same three launches per epoch with a member axis on the grid (forward
+ * and backward batch x n_members workgroups, Adam ceil(P / 256) x n_members); member m is the reference's run on the trajectories m * E
+ * .. (m + 1) * E - 1, E = n_trajectories / n_members. Every tensor of `learner` but the rollout exists once per member, stacked on a
+ * leading member axis in one contiguous tensor, and the learner's pointers address member 0: the 14 params, m, v, the 10 old_params,
+ * step int64 [n_members], stats_out float [n_members][n_epochs][3], rows / rows_out int64 [n_members][n_epochs][batch]. workspace:
+ * sgk_ppo_cnn_members_workspace_bytes(h, n_channels, batch, n_members) bytes, 8-byte aligned, owned by the caller: n_members slices of
+ * the single learner's layout (header, per-sample scalars, saved activations, per-sample gradients; each slice padded to 8 bytes).
+ * The rollout is shared: n_trajectories = all members' trajectories (sgk_convq_rollout_members' outputs), rows are global (step *
+ * n_trajectories + trajectory). Member m draws its trajectory from [0, E) with sgk_ppo_cnn_epochs' Philox call keyed by
+ * member_keys_dev[m] (uint64 [n_members], device; NULL: the handle's seed for every member) and its OWN step counter, then offsets it
+ * by m * E. A caller's row outside the rollout, or of a trajectory that is not member m's own, trains on the member's first row (step
+ * 0, trajectory m * E). The backward kernel forms the advantage statistics from its own member's samples only. All hyper-parameters
+ * are shared. The member instantiation of the kernels is used for every n_members, 1 included (where, with member_keys_dev NULL and
+ * valid rows, it leaves the bytes sgk_ppo_cnn_epochs leaves). No allocation, no host synchronisation, no atomics: can be recorded in
+ * a graph. SGK_ERR_INVALID for n_members outside 1 .. 65535, n_trajectories % n_members != 0, a NULL or misaligned workspace and
+ * whatever sgk_ppo_cnn_epochs refuses. */
+SGK_API int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *learner, int32_t n_members, const uint64_t *member_keys_dev);
+/* The workspace sgk_ppo_cnn_epochs_members needs, in bytes; -1 (sgk_last_error says why) for n_members < 1 or an unsupported
+ * n_channels, board shape or batch. */
+SGK_API int64_t sgk_ppo_cnn_members_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch, int32_t n_members);
 /* ReplayBuffer.add for every env (reference contain.py:15-17 via value.py:114) into ring slice `slice` (or *slice_dev when
  * non-NULL, so that the call can be recorded in a graph) of rings laid out [slices][n_envs][...]: phase 0, called before
  * sgk_step, stores the current boards as the transitions' state; phase 1, called after it, stores the boards as successor

@@ -886,8 +886,10 @@ static int convq_launch(sgk_env *h, const sgk_convq_weights *w, int mode, double
   return SGK_OK;
 }
 
-int sgk_convq_rollout(sgk_env *h, const sgk_convq_weights *w, int32_t mode, double epsilon, uint64_t draw_index0, int32_t n_steps,
-                      uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev) try {
+// sgk_convq_rollout (n_members 0: its own kernel) and sgk_convq_rollout_members (the member instantiation): the same checks
+static int convq_rollout_impl(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, int32_t mode, double epsilon, uint64_t draw_index0,
+                              int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
+                              sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) {
   SGK_CHECK_HANDLE(h);
   if (int rc = convq_weights_ok(w)) return rc;
   if (mode != 0 && mode != 1) return fail(SGK_ERR_INVALID, "mode must be 0 (epsilon-greedy) or 1 (categorical)");
@@ -898,12 +900,29 @@ int sgk_convq_rollout(sgk_env *h, const sgk_convq_weights *w, int32_t mode, doub
   sgk::Shard &s = h->sh;
   sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
   SGK_HIP(sgk::launch_convq_rollout(s, cw, w->n_channels, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev,
-                                    reinterpret_cast<uint32_t *>(recs_out_dev), h->stream));
+                                    reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev));
   SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
   s.lockstep_t += (uint64_t)n_steps;
   h->t_dev_stale = true;
   h->steps_issued += s.n * n_steps;
   return SGK_OK;
+}
+
+int sgk_convq_rollout(sgk_env *h, const sgk_convq_weights *w, int32_t mode, double epsilon, uint64_t draw_index0, int32_t n_steps,
+                      uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev) try {
+  return convq_rollout_impl(h, w, 0, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev, nullptr);
+} SGK_CATCH_STATUS
+
+int sgk_convq_rollout_members(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                              uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
+                              sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) try {
+  SGK_CHECK_HANDLE(h);
+  if (n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)n_members);
+  if (h->sh.n % n_members != 0)
+    return fail(SGK_ERR_INVALID, "n_envs (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                (long long)h->sh.n, (int)n_members);
+  return convq_rollout_impl(h, w, n_members, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev,
+                            member_metrics_dev);
 } SGK_CATCH_STATUS
 
 int sgk_convq_act(sgk_env *h, const sgk_convq_weights *w, double epsilon, uint64_t draw_index, const double *epsilon_dev,
@@ -1120,9 +1139,24 @@ int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batc
   return (int64_t)sgk::ppo_cnn_workspace_bytes(H, W, n_channels, batch);
 } SGK_CATCH_VALUE(-1)
 
-int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try {
+int64_t sgk_ppo_cnn_members_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch, int32_t n_members) try {
+  if (!h) return (int64_t)fail(SGK_ERR_INVALID, "handle is NULL");
+  const int H = h->sh.rules_host.height, W = h->sh.rules_host.width;
+  if (n_members < 1 || !sgk::ppo_cnn_shape_supported(H, W, n_channels) || batch < 2 || batch > 64) {
+    fail(SGK_ERR_INVALID, "sgk_ppo_cnn_members_workspace_bytes needs n_members >= 1, n_channels 4, 5 or 8, 2 <= batch <= 64 and a board of "
+                          "5x5, 6x5, 6x6, 6x8, 7x7, 7x8 or 7x9 (this level: %dx%d, n_channels %d, batch %d, n_members %d)", H, W,
+         (int)n_channels, (int)batch, (int)n_members);
+    return -1;
+  }
+  return (int64_t)n_members * (int64_t)sgk::ppo_cnn_members_stride_bytes(H, W, n_channels, batch);
+} SGK_CATCH_VALUE(-1)
+
+// sgk_ppo_cnn_epochs (n_members 0: its own kernels, the handle's seed) and sgk_ppo_cnn_epochs_members: the same checks
+static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
+  if (!L->workspace && n_members > 0)
+    return fail(SGK_ERR_INVALID, "workspace is NULL: sgk_ppo_cnn_epochs_members works in the caller's sgk_ppo_cnn_members_workspace_bytes()");
   const void *need[] = {L->states, L->actions, L->returns, L->lengths, L->step, L->workspace};
   for (const void *p : need)
     if (!p) return fail(SGK_ERR_INVALID, "NULL pointer in sgk_ppo_cnn_learner");
@@ -1149,8 +1183,21 @@ int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try {
   d.workspace = L->workspace;
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
   d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
-  SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream));
+  SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream, n_members, member_keys_dev));
   return SGK_OK;
+}
+
+int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try { return ppo_cnn_epochs_impl(h, L, 0, nullptr); } SGK_CATCH_STATUS
+
+int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev) try {
+  SGK_CHECK_HANDLE(h);
+  if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
+  if (n_members < 1 || n_members > 65535) return fail(SGK_ERR_INVALID, "n_members must be in 1 .. 65535 (got %d)", (int)n_members);
+  if (L->n_trajectories % n_members != 0)
+    return fail(SGK_ERR_INVALID, "n_trajectories (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                (long long)L->n_trajectories, (int)n_members);
+  if ((uintptr_t)L->workspace & 7u) return fail(SGK_ERR_INVALID, "workspace must be 8-byte aligned");
+  return ppo_cnn_epochs_impl(h, L, n_members, member_keys_dev);
 } SGK_CATCH_STATUS
 
 int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,

@@ -8,7 +8,7 @@
 // convolutions run as in sgk_convq_act (four waves, three barriers), wave 0 sums the outputs and draws, and its owner lanes step their
 // envs (the kernels' one step_one), store action and record, and re-draw their rows. No board, action or record crosses HBM between
 // steps except as trajectory output: per lockstep step the caller's four launches (forward + draw, board copy, sgk_step, record copy)
-// become one pass of this loop.
+// become one pass of this loop. sgk_convq_rollout_members runs the same loop for n_members independent bodies (ConvRolloutMemberArgs).
 #include "sgk_convq.h"
 
 namespace sgk {
@@ -36,6 +36,17 @@ struct ConvRolloutArgs {
   uint32_t *recs_out;    // [n_steps][n] step records or null
 };
 
+// sgk_convq_rollout_members: n_members independent conv bodies in one launch. Member m owns the envs m * member_envs .. (m + 1) *
+// member_envs - 1 and the m-th slice of each of the ten stacked weight tensors. A workgroup belongs to ONE member for the whole launch
+// (member_wgs consecutive workgroups each: the grid is n_members * member_wgs, and the hardware queues what is not resident), reads
+// that member's weights and walks that member's ceil(member_envs / ENVS) passes only, so a pass never straddles two members. Env
+// indices -- RNG keys, trajectory columns, episode arrays -- stay the shard's own.
+struct ConvRolloutMemberArgs : ConvRolloutArgs {
+  int64_t member_envs;        // envs per member
+  int32_t member_wgs;         // workgroups per member
+  long long *member_metrics;  // [n_members][SGK_METRICS_LEN]: each member's own episode sums / counts / maxima, or null
+};
+
 template <int ENV, int C>
 struct ConvRolloutLds {
   typedef ConvQGeom<ConvDims<ENV>::H, ConvDims<ENV>::W, C> G;
@@ -51,11 +62,21 @@ struct ConvRolloutLds {
 #ifndef CQ_ROLLOUT_WAVES_FOR
 #define CQ_ROLLOUT_WAVES_FOR(C) CQ_WAVES_FOR(C)
 #endif
-template <int ENV, int C>
+// the distance between two passes of a workgroup: the grid, or its member's workgroups
+template <bool MEMBERS, class Args>
+__device__ __forceinline__ int64_t cr_pass_step(const Args &a) {
+  if constexpr (MEMBERS) return a.member_wgs;
+  else return gridDim.x;
+}
+
+// MEMBERS = false is sgk_convq_rollout's kernel, as it was before the member axis; MEMBERS = true (sgk_convq_rollout_members, with one
+// member too) adds the member's offsets to the weight pointers and bounds the passes by the member's envs.
+template <int ENV, int C, bool MEMBERS>
 __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_kernel(
-    ConvRolloutArgs a, const float *__restrict__ w1r, const float *__restrict__ b1r, const float *__restrict__ w2r,
-    const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr, const float *__restrict__ whr,
-    const float *__restrict__ bhr, const float *__restrict__ wlr, const float *__restrict__ blr) {
+    typename std::conditional<MEMBERS, ConvRolloutMemberArgs, ConvRolloutArgs>::type a, const float *__restrict__ w1r,
+    const float *__restrict__ b1r, const float *__restrict__ w2r, const float *__restrict__ b2r, const float *__restrict__ wbr,
+    const float *__restrict__ bbr, const float *__restrict__ whr, const float *__restrict__ bhr, const float *__restrict__ wlr,
+    const float *__restrict__ blr) {
   constexpr int HH = ConvDims<ENV>::H, WW = ConvDims<ENV>::W;
   typedef ConvQGeom<HH, WW, C> G;
   typedef ConvRolloutLds<ENV, C> LD;
@@ -67,6 +88,15 @@ __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_
   int *act_sh = reinterpret_cast<int *>(convq_smem + LD::o_flags), *over_sh = act_sh + G::ENVS;
   SgkRules &R = *reinterpret_cast<SgkRules *>(convq_smem + LD::o_rules);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int member = 0, member_wg = 0;
+  if constexpr (MEMBERS) {
+    member = (int)blockIdx.x / a.member_wgs;
+    member_wg = (int)blockIdx.x - member * a.member_wgs;
+    const size_t m = (size_t)member;  // this member's slice of the ten stacked tensors
+    w1r += m * (C * G::K1); b1r += m * C; w2r += m * (C * G::K2); b2r += m * C; wbr += m * C; bbr += m * C; whr += m * (C * G::K2);
+    bhr += m * C;
+    wlr += m * (4 * G::NF); blr += m * 4;
+  }
   CqLane<G> L;
   cq_setup<G, WW, C>(L, WL, act, w1r, w2r, whr, wlr);
   // this lane's board bytes of a pass: element i = (env e, cell pos) of the row tile -> its place in plane 0
@@ -81,16 +111,22 @@ __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_
   }
   stage_rules(R, a.env.rules);  // ends with a workgroup barrier: weights, planes and rules are in place
   const int64_t n = a.env.n;
-  const int64_t n_pass = (n + G::ENVS - 1) / G::ENVS;
+  // the envs this workgroup's passes cover (the batch's, or its member's) and which of their passes are its own
+  int64_t first_env = 0, end_env = n;
+  if constexpr (MEMBERS) {
+    first_env = (int64_t)member * a.member_envs;
+    end_env = first_env + a.member_envs;
+  }
+  const int64_t n_pass = (end_env - first_env + G::ENVS - 1) / G::ENVS;
   const bool mask_finished = (a.env.flags & SGK_F_MASK_FINISHED) != 0;
   const bool owner = t < G::ENVS;  // lanes of wave 0: one env each
   EpisodeAcc acc;
   acc_init(acc);
-  for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-    const int64_t env0 = pass * G::ENVS;
+  for (int64_t pass = MEMBERS ? (int64_t)member_wg : (int64_t)blockIdx.x; pass < n_pass; pass += cr_pass_step<MEMBERS>(a)) {
+    const int64_t env0 = first_env + pass * G::ENVS;
     const int hz = (int)(pass >> 44);  // (always 0: see cq_network)
     const int64_t env = env0 + t;
-    const bool valid = owner && env < n;
+    const bool valid = owner && env < end_env;
     EnvState s = initial_state(R);
     if (valid) s = unpack_state(a.env.state[env]);
     load_episode_index<ENV>(s, a.env.n_resets, env, valid);
@@ -100,7 +136,7 @@ __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_
       over_sh[t] = (mask_finished && s.over) ? 1 : 0;
     }
     uint32_t rec = 0;
-    const int64_t left = n - env0;
+    const int64_t left = end_env - env0;
     const int lim = left < G::ENVS ? (int)left : G::ENVS;  // envs of this pass that exist
     for (int k = 0; k < a.n_steps; ++k) {
       __syncthreads();  // the rows (and the finished flags) of this step are complete; the previous step's sums have been read
@@ -170,12 +206,18 @@ __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_
     __syncthreads();  // nobody still reads this pass's rows when the next pass's owners draw theirs
   }
   acc_flush(acc, a.env.metrics);
+  if constexpr (MEMBERS) {
+    if (a.member_metrics) acc_flush_row(acc, a.member_metrics + (size_t)member * SGK_METRICS_LEN);  // the same reduction, this member's row
+  }
 }
 
+// n_members == 0: sgk_convq_rollout's own kernel; >= 1: the member instantiation (sgk_convq_rollout_members)
 hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0, int32_t n_steps,
-                                uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st) {
+                                uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st, int n_members,
+                                int64_t *member_metrics) {
   (void)hipGetLastError();
-  ConvRolloutArgs a;
+  if (n_members < 0 || (n_members > 0 && sh.n % n_members != 0)) return hipErrorInvalidValue;
+  ConvRolloutMemberArgs a;
   a.env = make_step_args(sh, nullptr, flags);
   a.eps = eps;
   a.draw0 = draw0;
@@ -184,18 +226,31 @@ hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_ch
   a.states_out = states_out;
   a.actions_out = actions_out;
   a.recs_out = recs_out;
+  a.member_envs = n_members > 0 ? sh.n / n_members : sh.n;
+  a.member_wgs = 0;
+  a.member_metrics = reinterpret_cast<long long *>(member_metrics);
 #define SGK_CONVQ_ROLLOUT(E, CV)                                                                                           \
   do {                                                                                                                     \
     typedef ConvRolloutLds<E, CV> LD;                                                                                      \
     static_assert(LD::bytes <= 160u * 1024u, "convq rollout LDS plan");                                                   \
     if (ConvDims<E>::H != sh.rules_host.height || ConvDims<E>::W != sh.rules_host.width) return hipErrorInvalidValue;      \
     constexpr size_t lds = LD::bytes;                                                                                      \
-    const int64_t n_pass = (sh.n + LD::G::ENVS - 1) / LD::G::ENVS;                                                         \
-    hipError_t ae = allow_dynamic_lds<convq_rollout_kernel<E, CV>>(sh.device, (int)lds);                                   \
-    if (ae != hipSuccess) return ae;                                                                                       \
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_ROLLOUT_WAVES_FOR(CV), (160u * 1024u) / lds));         \
-    const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
-    convq_rollout_kernel<E, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(a, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl); \
+    if (n_members == 0) {                                                                                                  \
+      const int64_t n_pass = (sh.n + LD::G::ENVS - 1) / LD::G::ENVS;                                                       \
+      hipError_t ae = allow_dynamic_lds<convq_rollout_kernel<E, CV, false>>(sh.device, (int)lds);                          \
+      if (ae != hipSuccess) return ae;                                                                                     \
+      const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                \
+      convq_rollout_kernel<E, CV, false><<<dim3(grid), dim3(CQ_WG), lds, st>>>(a, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl); \
+    } else {                                                                                                               \
+      /* a member's workgroups: one per pass while all members' fit the chip (one member: the single kernel's grid), at least one */ \
+      const int64_t n_pass = (a.member_envs + LD::G::ENVS - 1) / LD::G::ENVS;                                              \
+      hipError_t ae = allow_dynamic_lds<convq_rollout_kernel<E, CV, true>>(sh.device, (int)lds);                           \
+      if (ae != hipSuccess) return ae;                                                                                     \
+      a.member_wgs = grid_for(n_pass, std::max(sh.n_cus * per_cu / n_members, 1));                                         \
+      if ((int64_t)n_members * a.member_wgs > (int64_t)INT32_MAX) return hipErrorInvalidValue;                             \
+      convq_rollout_kernel<E, CV, true><<<dim3(n_members * a.member_wgs), dim3(CQ_WG), lds, st>>>(a, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl); \
+    }                                                                                                                      \
   } while (0)
   SGK_DISPATCH_ENV(sh.env_id, {
     if (n_channels == 5) SGK_CONVQ_ROLLOUT(E, 5);

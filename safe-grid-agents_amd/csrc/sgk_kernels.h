@@ -104,9 +104,12 @@ struct ConvQWeights {
 // mode 0: epsilon-greedy on the four scores (DeepQAgent.act_explore); 1: Categorical(logits = scores).sample() (PPOBaseAgent.act_explore)
 hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, uint8_t *actions, float *scores, double eps, uint64_t draw,
                             const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
-// n_steps of {conv forward, draw, env.step} in one launch (sgk_convq_rollout.hip); outputs as for launch_policy_rollout
+// n_steps of {conv forward, draw, env.step} in one launch (sgk_convq_rollout.hip); outputs as for launch_policy_rollout.
+// n_members >= 1 (sgk_convq_rollout_members; 0: sgk_convq_rollout's own kernel): `w` addresses member 0 of the ten weight tensors stacked
+// [n_members][...], member m acts in the envs m * n / n_members ..; member_metrics as for launch_policy_rollout
 hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0, int32_t n_steps,
-                                uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st);
+                                uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
+                                int n_members = 0, int64_t *member_metrics = nullptr);
 // DeepQAgent.learn as one kernel (sgk_learn.hip); all pointers are device pointers
 struct DqnLearner {
   const int8_t *states, *successors;
@@ -194,7 +197,13 @@ struct PpoCnnLearner {
 };
 bool ppo_cnn_shape_supported(int height, int width, int n_channels);
 size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch);
-hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st);
+size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int batch);  // one member's slice: the above, 8-byte padded
+// n_members >= 1 (sgk_ppo_cnn_epochs_members; 0: sgk_ppo_cnn_epochs' own kernels): the member instantiation of the three kernels, a
+// member axis on the grid. Every tensor of P but the rollout is stacked [n_members][...] and P addresses member 0, the workspace is
+// n_members slices of ppo_cnn_members_stride_bytes(); member m draws its rows from the trajectories m * n_trajectories / n_members .. with the
+// key member_keys[m] (null: the shard's seed) and its own step counter
+hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members = 0,
+                                 const uint64_t *member_keys = nullptr);
 hipError_t launch_discounted_returns(const Shard &sh, const float *rewards, const int32_t *lengths, const float *gamma_pow,
                                      float *returns, int64_t n, int t_max, hipStream_t st);
 hipError_t launch_render_rgb(const Shard &sh, uint8_t *dst, hipStream_t st);

@@ -21,6 +21,8 @@
 // a sample ((1 + 5 C) padded planes + the parameters: <= 50 KB) live in one workgroup's LDS; the convolutions are so small (~1e5
 // multiply-adds per sample and epoch) that one lane per output with the weights in LDS is latency- and not FLOP-bound. Every sum
 // runs in a fixed order: a call is deterministic and a captured replay equals the eager call bit for bit.
+// sgk_ppo_cnn_epochs_members: the same three launches for n_members independent learners, the member on blockIdx.y (the MEMBERS
+// instantiations below); every member works in its own slice of the workspace and reads only its own samples.
 #include <algorithm>
 
 #include "sgk_device.h"
@@ -60,6 +62,12 @@ size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch)
   return sizeof(float) * (PC_HDR + PC_SCAL + (size_t)batch * (save + p));
 }
 
+// a member's slice of sgk_ppo_cnn_epochs_members' workspace: the single learner's layout, padded so that every slice's int64 header
+// and rows stay 8-byte aligned
+size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int batch) {
+  return (ppo_cnn_workspace_bytes(height, width, n_channels, batch) + 7) & ~(size_t)7;
+}
+
 struct PpoCnnArgs {
   const int8_t *states;
   const uint8_t *actions;
@@ -77,7 +85,20 @@ struct PpoCnnArgs {
   int32_t batch;
   uint64_t seed;
   float lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
+  // the member instantiation only (sgk_ppo_cnn_epochs_members): blockIdx.y = member m. Every tensor above but the rollout is stacked
+  // [n_members][...] and the pointers address member 0; the workspace is n_members slices of ws_stride floats; member m draws from
+  // the trajectories m * E .. (m + 1) * E - 1 with member_keys[m] (null: `seed`) and step[m]
+  int64_t E;
+  const uint64_t *member_keys;
+  size_t ws_stride;
+  int32_t n_epochs;
 };
+
+// this workgroup's member (0 without the member axis) and what it owns
+template <bool MEMBERS>
+__device__ __forceinline__ size_t pc_member() { return MEMBERS ? (size_t)blockIdx.y : (size_t)0; }
+template <bool MEMBERS>
+__device__ __forceinline__ float *pc_ws(const PpoCnnArgs &a) { return MEMBERS ? a.ws + pc_member<MEMBERS>() * a.ws_stride : a.ws; }
 
 template <class G>
 __device__ __forceinline__ int pc_tensor_size(int k) {
@@ -86,13 +107,14 @@ __device__ __forceinline__ int pc_tensor_size(int k) {
   return off[k + 1] - off[k];
 }
 
-// the first n_tensors parameter tensors, flattened, into LDS
+// the first n_tensors parameter tensors (member `member`'s slice of each), flattened, into LDS
 template <class G>
-__device__ __forceinline__ void pc_stage(float *dst, const float *const *src, int n_tensors) {
+__device__ __forceinline__ void pc_stage(float *dst, const float *const *src, int n_tensors, size_t member) {
   int base = 0;
   for (int k = 0; k < n_tensors; ++k) {
     const int n = pc_tensor_size<G>(k);
-    for (int i = threadIdx.x; i < n; i += PC_WG) dst[base + i] = src[k][i];
+    const float *sk = src[k] + member * (size_t)n;
+    for (int i = threadIdx.x; i < n; i += PC_WG) dst[base + i] = sk[i];
     base += n;
   }
 }
@@ -163,7 +185,9 @@ __device__ __forceinline__ void pc_trunk(float *act, const float *w) {
   __syncthreads();
 }
 
-template <int HH, int WW, int C>
+// MEMBERS = false: sgk_ppo_cnn_epochs' kernels, grid (batch) resp. (ceil(P / 256)); MEMBERS = true: sgk_ppo_cnn_epochs_members', a
+// member axis blockIdx.y on the same grids (with one member too). The arithmetic of a sample does not depend on the flag.
+template <int HH, int WW, int C, bool MEMBERS>
 __global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, int epoch) {
   typedef PcGeom<HH, WW, C> G;
   __shared__ __attribute__((aligned(16))) float act[G::ACT_PLANES * G::PL];
@@ -172,24 +196,36 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, in
   __shared__ float red[8 + 8 * (PC_WG / 64)];
   __shared__ long long row_s;
   const int b = blockIdx.x, t = threadIdx.x, B = a.batch;
-  float *sc = a.ws + PC_HDR + b * PC_SC;
-  const long long step = *a.step;  // Adam steps done before this epoch: the key of the draws
+  const size_t mem = pc_member<MEMBERS>();
+  float *ws = pc_ws<MEMBERS>(a);
+  float *sc = ws + PC_HDR + b * PC_SC;
+  const long long step = a.step[mem];  // Adam steps done before this epoch: the key of the draws
+  const long long slot = MEMBERS ? ((long long)mem * a.n_epochs + epoch) * B + b : (long long)epoch * B + b;  // in rows / rows_out
+  const long long n0 = MEMBERS ? (long long)mem * a.E : 0, NE = MEMBERS ? a.E : a.N;  // this learner's trajectories: n0 .. n0 + NE - 1
+  uint64_t seed = a.seed;
+  if (MEMBERS && a.member_keys) seed = a.member_keys[mem];
   // ---- the row: the caller's, or sgk_ppo_epochs' draw (16 candidates per round, the first valid one in candidate order) ----
   if (t < 64) {
     const int lane = t;
     long long row;
     if (a.rows) {
-      row = a.rows[(long long)epoch * B + b];
-      row = row < 0 ? 0 : (row >= (long long)a.T * a.N ? (long long)a.T * a.N - 1 : row);  // a bad row must not leave the rollout
+      row = a.rows[slot];
+      if (MEMBERS) {  // a row outside the rollout or of another member's trajectory: the member's first row (step 0, trajectory n0)
+        const bool inside = row >= 0 && row < (long long)a.T * a.N;
+        const long long nn = inside ? row % a.N : -1;
+        if (nn < n0 || nn >= n0 + NE) row = n0;
+      } else {
+        row = row < 0 ? 0 : (row >= (long long)a.T * a.N ? (long long)a.T * a.N - 1 : row);  // a bad row must not leave the rollout
+      }
     } else {
-      int tt = 0, nn = 0;
+      int tt = 0, nn = (int)n0;
       for (int round = 0; round < 64; ++round) {
         bool ok = false;
         int t_c = 0, n_c = 0;
         if (lane < 16) {
           uint32_t x[4];
-          philox4x32_10((uint32_t)(b * 16 + lane), (uint32_t)round, (uint32_t)step, 5u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), x);
-          n_c = (int)__umul64hi(((unsigned long long)x[0] << 32) | x[1], (unsigned long long)a.N);
+          philox4x32_10((uint32_t)(b * 16 + lane), (uint32_t)round, (uint32_t)step, 5u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+          n_c = (int)n0 + (int)__umul64hi(((unsigned long long)x[0] << 32) | x[1], (unsigned long long)NE);
           t_c = (int)__umulhi(x[2], (uint32_t)a.T);
           ok = t_c < a.lengths[n_c];
         }
@@ -209,13 +245,13 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, in
       sc[9] = a.returns[nn * a.T + tt];
       reinterpret_cast<int *>(sc)[10] = (int)(a.actions[row] & 3);
       *reinterpret_cast<long long *>(sc + 12) = row;
-      if (a.rows_out) a.rows_out[(long long)epoch * B + b] = row;
-      if (b == 0) *reinterpret_cast<long long *>(a.ws) = step;
+      if (a.rows_out) a.rows_out[slot] = row;
+      if (b == 0) *reinterpret_cast<long long *>(ws) = step;
     }
   }
   for (int i = t; i < G::ACT_PLANES * G::PL; i += PC_WG) act[i] = 0.0f;
-  pc_stage<G>(wcur, a.p, 14);
-  pc_stage<G>(wold, a.o, 10);
+  pc_stage<G>(wcur, a.p, 14, mem);
+  pc_stage<G>(wold, a.o, 10, mem);
   __syncthreads();
   {
     const int8_t *board = a.states + row_s * G::NC;
@@ -238,7 +274,7 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, in
   pc_linear<G, 1>(act, G::CH, wcur + G::o_lv, wcur + G::o_lvb, red);
   if (t == 0) sc[4] = red[0];
   // ---- the activations the backward pass needs ----
-  float *save = a.ws + PC_HDR + PC_SCAL + (size_t)b * G::SAVE;
+  float *save = ws + PC_HDR + PC_SCAL + (size_t)b * G::SAVE;
   for (int i = t; i < G::SAVE; i += PC_WG) {
     const int pl = i / G::NC, cell = i - pl * G::NC;
     save[i] = act[(G::H1 + pl) * G::PL + pc_cell<G>(cell)];
@@ -288,22 +324,24 @@ __device__ __forceinline__ void pc_input_grad(const float *act, int g_plane, con
   }
 }
 
-template <int HH, int WW, int C>
+template <int HH, int WW, int C, bool MEMBERS>
 __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, int epoch) {
   typedef PcGeom<HH, WW, C> G;
   __shared__ __attribute__((aligned(16))) float act[G::BWD_PLANES * G::PL];
   __shared__ __attribute__((aligned(16))) float w[G::P];
   __shared__ float dout[8];
   const int b = blockIdx.x, t = threadIdx.x, B = a.batch;
-  const float *scal = a.ws + PC_HDR;
+  const size_t mem = pc_member<MEMBERS>();
+  float *ws = pc_ws<MEMBERS>(a);
+  const float *scal = ws + PC_HDR;  // this member's own samples
   for (int i = t; i < G::BWD_PLANES * G::PL; i += PC_WG) act[i] = 0.0f;
-  pc_stage<G>(w, a.p, 14);
+  pc_stage<G>(w, a.p, 14, mem);
   __syncthreads();
   {
     const long long row = *reinterpret_cast<const long long *>(scal + b * PC_SC + 12);
     const int8_t *board = a.states + row * G::NC;
     for (int i = t; i < G::NC; i += PC_WG) act[G::X * G::PL + pc_cell<G>(i)] = (float)board[i];
-    const float *save = a.ws + PC_HDR + PC_SCAL + (size_t)b * G::SAVE;
+    const float *save = ws + PC_HDR + PC_SCAL + (size_t)b * G::SAVE;
     for (int i = t; i < G::SAVE; i += PC_WG) {
       const int pl = i / G::NC, cell = i - pl * G::NC;
       act[(G::H1 + pl) * G::PL + pc_cell<G>(cell)] = save[i];
@@ -360,11 +398,12 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, i
       const float pl = -__ockl_wfred_add_f32(live ? fminf(s1, s2) : 0.0f) * invB;
       const float vl = __ockl_wfred_add_f32(live ? (v - r) * (v - r) : 0.0f) * invB;
       const float en = __ockl_wfred_add_f32(live ? ent : 0.0f) * invB;
-      if (lane == 0) { a.stats_out[epoch * 3] = pl; a.stats_out[epoch * 3 + 1] = vl; a.stats_out[epoch * 3 + 2] = en; }
+      float *so = a.stats_out + (MEMBERS ? (mem * a.n_epochs + epoch) * 3 : (size_t)epoch * 3);
+      if (lane == 0) { so[0] = pl; so[1] = vl; so[2] = en; }
     }
   }
   __syncthreads();
-  float *g = a.ws + PC_HDR + PC_SCAL + (size_t)B * G::SAVE + (size_t)b * G::P;  // this sample's gradient row
+  float *g = ws + PC_HDR + PC_SCAL + (size_t)B * G::SAVE + (size_t)b * G::P;  // this sample's gradient row
   // ---- the linear heads: weight / bias gradients, and the heads' pre-activation gradients (ReLU') into GA / GC ----
   for (int f = t; f < G::NF; f += PC_WG) {
     const int c = f / G::NC, cell = f - c * G::NC, o = pc_cell<G>(cell);
@@ -420,13 +459,15 @@ __device__ __forceinline__ float pc_adam(float p, float &m, float &v, float g, f
   return p - lr_bc1 * (m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * inv_bc2_sqrt + eps));  // (sgk_ppo_epochs' adam_plain)
 }
 
-template <int HH, int WW, int C>
+template <int HH, int WW, int C, bool MEMBERS>
 __global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(PpoCnnArgs a) {
   typedef PcGeom<HH, WW, C> G;
   const int e = blockIdx.x * PC_WG + threadIdx.x;
-  const long long step = *reinterpret_cast<const long long *>(a.ws);  // (the forward launch's copy: *a.step is written below)
+  const size_t mem = pc_member<MEMBERS>();
+  const float *ws = pc_ws<MEMBERS>(a);
+  const long long step = *reinterpret_cast<const long long *>(ws);  // (the forward launch's copy: the step counter is written below)
   if (e < G::P) {
-    const float *gr = a.ws + PC_HDR + PC_SCAL + (size_t)a.batch * G::SAVE + e;
+    const float *gr = ws + PC_HDR + PC_SCAL + (size_t)a.batch * G::SAVE + e;
     float gs = 0.0f;
     for (int b = 0; b < a.batch; ++b) gs += gr[(size_t)b * G::P];
     constexpr int off[14] = {G::o_w1, G::o_b1, G::o_w2, G::o_b2, G::o_wb, G::o_bb, G::o_wa, G::o_ba, G::o_la, G::o_lab, G::o_wv, G::o_bv,
@@ -435,14 +476,16 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(PpoCnnArgs a) {
 #pragma unroll
     for (int j = 1; j < 14; ++j) k += e >= off[j] ? 1 : 0;
     const int le = e - off[k];
+    const size_t mo = MEMBERS ? mem * (size_t)pc_tensor_size<G>(k) : (size_t)0;  // this member's slice of tensor k
+    float *pk = a.p[k] + mo, *mk = a.m[k] + mo, *vk = a.v[k] + mo;
     const float lr_bc1 = a.lr / (float)(1.0 - pow((double)a.beta1, (double)(step + 1)));
     const float inv_bc2_sqrt = 1.0f / sqrtf((float)(1.0 - pow((double)a.beta2, (double)(step + 1))));
-    float m = a.m[k][le], v = a.v[k][le];
-    a.p[k][le] = pc_adam(a.p[k][le], m, v, gs, lr_bc1, inv_bc2_sqrt, a.beta1, a.beta2, a.eps);
-    a.m[k][le] = m;
-    a.v[k][le] = v;
+    float m = mk[le], v = vk[le];
+    pk[le] = pc_adam(pk[le], m, v, gs, lr_bc1, inv_bc2_sqrt, a.beta1, a.beta2, a.eps);
+    mk[le] = m;
+    vk[le] = v;
   }
-  if (e == 0) *a.step = step + 1;
+  if (e == 0) a.step[mem] = step + 1;
 }
 
 bool ppo_cnn_shape_supported(int height, int width, int n_channels) {
@@ -451,26 +494,28 @@ bool ppo_cnn_shape_supported(int height, int width, int n_channels) {
   return shape && (n_channels == 4 || n_channels == 5 || n_channels == 8);
 }
 
-template <int HH, int WW, int C>
-static hipError_t launch_ppo_cnn_shape(const PpoCnnArgs &a, int n_epochs, hipStream_t st) {
+template <int HH, int WW, int C, bool MEMBERS>
+static hipError_t launch_ppo_cnn_shape(const PpoCnnArgs &a, int n_epochs, int n_members, hipStream_t st) {
   typedef PcGeom<HH, WW, C> G;
   static_assert(G::P == pc_params(HH, WW, C), "parameter map");
+  const unsigned ny = MEMBERS ? (unsigned)n_members : 1u;
   for (int epoch = 0; epoch < n_epochs; ++epoch) {
-    ppo_cnn_forward_kernel<HH, WW, C><<<dim3(a.batch), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_backward_kernel<HH, WW, C><<<dim3(a.batch), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_adam_kernel<HH, WW, C><<<dim3((G::P + PC_WG - 1) / PC_WG), dim3(PC_WG), 0, st>>>(a);
+    ppo_cnn_forward_kernel<HH, WW, C, MEMBERS><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
+    ppo_cnn_backward_kernel<HH, WW, C, MEMBERS><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
+    ppo_cnn_adam_kernel<HH, WW, C, MEMBERS><<<dim3((G::P + PC_WG - 1) / PC_WG, ny), dim3(PC_WG), 0, st>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st) {
+hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys) {
   (void)hipGetLastError();
   const int H = sh.rules_host.height, W = sh.rules_host.width, C = P.n_channels;
   if (!ppo_cnn_shape_supported(H, W, C) || P.batch < 2 || P.batch > 64 || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 ||
       P.n_trajectories >= (1ll << 31) || !P.workspace)
     return hipErrorInvalidValue;
+  if (n_members < 0 || n_members > 65535 || (n_members > 0 && P.n_trajectories % n_members != 0)) return hipErrorInvalidValue;  // (gridDim.y)
   PpoCnnArgs a;
   a.states = P.states; a.actions = P.actions; a.returns = P.returns; a.lengths = P.lengths;
   a.T = P.horizon; a.N = P.n_trajectories;
@@ -481,11 +526,20 @@ hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStr
   a.batch = P.batch; a.seed = sh.seed;
   a.lr = (float)P.lr; a.beta1 = (float)P.beta1; a.beta2 = (float)P.beta2; a.eps = (float)P.eps;
   a.clipping = (float)P.clipping; a.critic_coeff = (float)P.critic_coeff; a.entropy_bonus = (float)P.entropy_bonus;
+  a.E = n_members > 0 ? P.n_trajectories / n_members : P.n_trajectories;
+  a.member_keys = member_keys;
+  a.ws_stride = ppo_cnn_members_stride_bytes(H, W, C, P.batch) / sizeof(float);
+  a.n_epochs = P.n_epochs;
 #define SGK_PC_LAUNCH_C(HV, WV)                                                                                            \
   do {                                                                                                                     \
-    if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5>(a, P.n_epochs, st);                                                 \
-    if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4>(a, P.n_epochs, st);                                                 \
-    return launch_ppo_cnn_shape<HV, WV, 8>(a, P.n_epochs, st);                                                             \
+    if (n_members > 0) {                                                                                                   \
+      if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, true>(a, P.n_epochs, n_members, st);                              \
+      if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, true>(a, P.n_epochs, n_members, st);                              \
+      return launch_ppo_cnn_shape<HV, WV, 8, true>(a, P.n_epochs, n_members, st);                                          \
+    }                                                                                                                      \
+    if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, false>(a, P.n_epochs, 1, st);                                       \
+    if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, false>(a, P.n_epochs, 1, st);                                       \
+    return launch_ppo_cnn_shape<HV, WV, 8, false>(a, P.n_epochs, 1, st);                                                   \
   } while (0)
   if (H == 5 && W == 5) SGK_PC_LAUNCH_C(5, 5);
   if (H == 6 && W == 5) SGK_PC_LAUNCH_C(6, 5);

@@ -7,6 +7,7 @@ from .agents import (AGENT_MAP, BatchedTabularQAgent, DeepQAgent, Experience, Ex
                      ReplayBuffer, Rollout, SingleActionAgent, TabularQAgent)
 from .ppo import BatchedPPOAgent, PPOBaseAgent, PPOCNNAgent, PPOMLPAgent, discounted_returns_f32
 from .ppo_population import BatchedPPOPopulation, default_member_seed, stack_state_dicts, unstack_state_dict
+from .ppo_cnn_population import BatchedPPOCNNPopulation
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
 from .deepq_population import BatchedDeepQPopulation
 from .envs import ENV_IDS, ENV_MAP, BatchedGridworldEnv, GridworldEnv, make
@@ -22,7 +23,7 @@ __all__ = [
     "make", "GridworldEnv", "BatchedGridworldEnv",
     "RandomAgent", "SingleActionAgent", "TabularQAgent", "DeepQAgent", "BatchedTabularQAgent", "BatchedDeepQAgent", "BatchedDeepQPopulation", "DeviceReplay",
     "ReplayBuffer", "Experience", "ExperienceBatch", "Rollout",
-    "BatchedPPOAgent", "batched_ppo_learn", "BatchedPPOPopulation", "population_ppo_learn", "default_member_seed", "stack_state_dicts",
+    "BatchedPPOAgent", "batched_ppo_learn", "BatchedPPOPopulation", "BatchedPPOCNNPopulation", "population_ppo_learn", "default_member_seed", "stack_state_dicts",
     "unstack_state_dict", "PPOBaseAgent", "PPOMLPAgent", "PPOCNNAgent", "discounted_returns_f32",
     "whiler", "tabq_learn", "dqn_learn", "ppo_learn", "default_eval", "dqn_warmup", "noop_warmup",
     "batched_random_rollout", "batched_tabq_learn", "batched_default_eval", "batched_gather_rollout", "BatchedRollout",

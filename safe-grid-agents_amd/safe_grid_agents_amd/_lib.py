@@ -155,12 +155,16 @@ _SIGNATURES = {
     "sgk_convq_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_uint64, _V, _V, _V]),
     "sgk_convq_rollout": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.c_double, ctypes.c_uint64, ctypes.c_int32,
                                          ctypes.c_uint32, _V, _V, _V]),
+    "sgk_convq_rollout_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                                 ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V]),
     "sgk_step_store": (ctypes.c_int, [_V, _V, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
     "sgk_reset_done_store": (ctypes.c_int, [_V, ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
     "sgk_ppo_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner)]),
     "sgk_ppo_epochs_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner), ctypes.c_int32, _V]),
     "sgk_ppo_cnn_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner)]),
     "sgk_ppo_cnn_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
+    "sgk_ppo_cnn_epochs_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), ctypes.c_int32, _V]),
+    "sgk_ppo_cnn_members_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "sgk_replay_store": (ctypes.c_int, [_V, ctypes.c_int32, _V, ctypes.c_int32, ctypes.c_int64, _V, _V, _V, _V, _V, _V]),
     "sgk_categorical_sample": (ctypes.c_int, [_V, _V, ctypes.c_uint64, _V, _V]),
     "sgk_policy_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_uint64, _V, _V, _V]),

@@ -890,6 +890,69 @@ class BatchedGridworldEnv:
             _lib.check(_lib.ERR_INVALID)
         return int(nbytes)
 
+    def _member_convq_weights(self, weights, n_members, n_channels, n_layers):
+        """sgk_convq_weights addressing member 0 of float32 device tensors stacked on a leading member axis: w1 [M, C, 1, 3, 3], b1
+        [M, C], w2 [M, C, C, 3, 3], b2, wb [M, C, 1, 1, 1], bb, wh [M, C, C, 3, 3], bh, wl [M, 4, C * cells], bl [M, 4]."""
+        C, m = int(n_channels), int(n_members)
+        shapes = {"w1": (m, C, 1, 3, 3), "b1": (m, C), "w2": (m, C, C, 3, 3), "b2": (m, C), "wb": (m, C, 1, 1, 1), "bb": (m, C),
+                  "wh": (m, C, C, 3, 3), "bh": (m, C), "wl": (m, 4, C * self.n_cells), "bl": (m, 4)}
+        for k, shape in shapes.items():
+            if k not in weights:
+                raise ValueError("weights lack %r" % k)
+            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
+        return _lib.SgkConvQWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1", "b1", "w2", "b2", "wb", "bb", "wh", "bh", "wl", "bl")),
+                                    C, int(n_layers))
+
+    def convq_rollout_members(self, weights, n_members, n_steps, n_channels, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False,
+                              states=None, actions=None, recs=None, mask_finished=False, member_metrics=None, n_layers=2):
+        """convq_rollout for n_members independent conv bodies in ONE HIP launch (sgk_convq_rollout_members): member m acts in the envs
+        m * E .. (m + 1) * E - 1 (E = N / n_members) with slice m of `weights`, tensors stacked on a leading member axis (see
+        _member_convq_weights). Outputs as for convq_rollout; member_metrics: int64 [n_members, 16] on this device that each member's
+        episodes are also booked in (sums added, maxima raised), or None."""
+        n_members = int(n_members)
+        if n_members < 1 or self.n_envs % n_members:
+            raise ValueError("n_envs (%d) is not a multiple of n_members (%d)" % (self.n_envs, n_members))
+        w = self._member_convq_weights(weights, n_members, n_channels, n_layers)
+        if mode not in ("greedy", "sample"):
+            raise ValueError("mode must be 'greedy' or 'sample'")
+
+        def ptr(t, shape, what, dtype):
+            if t is None:
+                return None
+            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
+
+        n = self.n_envs
+        args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
+                ptr(recs, (n_steps, n, 4), "recs", "int8"), ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"))
+        self._version += 1
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_convq_rollout_members(
+            self._h.ptr, ctypes.byref(w), n_members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
+            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
+        self._sync_lib_to_torch()
+
+    def ppo_cnn_members_workspace_bytes(self, n_channels, batch, n_members):
+        """Bytes of device workspace sgk_ppo_cnn_epochs_members needs on this level for n_members members with n_channels and batch
+        rows; SgkError when unsupported."""
+        nbytes = self.lib.sgk_ppo_cnn_members_workspace_bytes(self._h.ptr, int(n_channels), int(batch), int(n_members))
+        if nbytes < 0:
+            _lib.check(_lib.ERR_INVALID)
+        return int(nbytes)
+
+    def ppo_cnn_epochs_members(self, learner, n_members, member_keys=None):
+        """One learn() call of n_members independent PPOCNNAgents, three HIP launches per epoch (sgk_ppo_cnn_epochs_members); `learner`
+        is a filled _lib.SgkPpoCnnLearner addressing member 0 of the stacked tensors, whose workspace holds
+        ppo_cnn_members_workspace_bytes() bytes; member_keys a uint64-as-int64 [n_members] device tensor or None."""
+        n_members = int(n_members)
+        if n_members < 1 or int(learner.n_trajectories) % n_members:
+            raise ValueError("n_trajectories (%d) is not a multiple of n_members (%d)" % (int(learner.n_trajectories), n_members))
+        kp = None
+        if member_keys is not None:
+            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(n_members,), dtypes=("int64",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_ppo_cnn_epochs_members(self._h.ptr, ctypes.byref(learner), n_members, kp))
+        self._sync_lib_to_torch()
+
     def discounted_returns(self, rewards, discount, lengths=None, out=None):
         """PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186) for a batch: rewards float32
         [n_trajectories, T] on this GPU (lengths int32 [n_trajectories] optional) -> returns of the same shape, with the

@@ -333,7 +333,7 @@ def batched_tabq_learn(agent, env, n_steps, cheat=False, fused=True, chunk=100):
 
 
 def population_ppo_learn(pop, env, history=None, cheat=False):
-    """batched_ppo_learn for a BatchedPPOPopulation: every member gathers one rollout of its E episodes under its own old policy
+    """batched_ppo_learn for a BatchedPPOPopulation or a BatchedPPOCNNPopulation: every member gathers one rollout of its E episodes under its own old policy
     (one launch), runs its epochs (one launch) and syncs. Returns (per-member BatchMetrics of the gathered episodes, their aggregate)."""
     env.metrics_reset()
     pop.reset_member_metrics()

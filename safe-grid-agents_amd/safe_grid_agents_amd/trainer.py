@@ -34,8 +34,8 @@ _CORE_FLAGS = [
     # RCCL metrics all-reduce per reporting period). `python -m safe_grid_agents_amd --devices G ...` starts the G ranks itself;
     # under torch.distributed.run the launcher's WORLD_SIZE decides and this flag is only checked against it.
     ("devices", "G", dict(type=int, default=1)),
-    # extension: with ppo-mlp, M independent agents (BatchedPPOPopulation) of `--rollouts` envs each in one batch of N = M x rollouts
-    # envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree. With deep-q, M independent agents
+    # extension: with ppo-mlp or ppo-cnn, M independent agents (BatchedPPOPopulation / BatchedPPOCNNPopulation) of `--rollouts` envs each
+    # in one batch of N = M x rollouts envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree. With deep-q, M independent agents
     # (BatchedDeepQPopulation) of N / M envs each: the batch comes from -N, a multiple of M.
     ("members", "M", dict(type=int, default=0)),
 ]
@@ -75,7 +75,7 @@ _AGENT_FLAGS = {
                ("n-channels", "ch", dict(type=int, default=5)),
                _MEMBERS],
     "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS],
-    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG],
+    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS],
 }
 
 
@@ -178,11 +178,12 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     from .agents import BatchedTabularQAgent
     from .loops import batched_default_eval, batched_ppo_learn, population_ppo_learn
     from .ppo import BatchedPPOAgent
+    from .ppo_cnn_population import BatchedPPOCNNPopulation
     from .ppo_population import BatchedPPOPopulation
 
     members = int(getattr(args, "members", 0) or 0)
     if members:
-        members_n_envs(args)  # ppo-mlp: N = M x rollouts; deep-q: -N, a multiple of M
+        members_n_envs(args)  # ppo-mlp, ppo-cnn: N = M x rollouts; deep-q: -N, a multiple of M
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -217,7 +218,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         agent.warmup(slices)  # dqn_warmup (warmup.py:8-23) of every member: random-action transitions fill the replay
         env.reset()
     elif members:
-        agent = BatchedPPOPopulation(env, args, members)
+        agent = (BatchedPPOCNNPopulation if args.agent_alias == "ppo-cnn" else BatchedPPOPopulation)(env, args, members)
     elif args.agent_alias in ("ppo-mlp", "ppo-cnn"):
         import torch
 
@@ -240,7 +241,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         agent = None
     else:
         raise KeyError("train_batched supports tabular-q, deep-q, ppo-mlp, ppo-cnn and random, not %r" % (args.agent_alias,))
-    ppo = isinstance(agent, (BatchedPPOAgent, BatchedPPOPopulation))
+    ppo = isinstance(agent, (BatchedPPOAgent, BatchedPPOPopulation, BatchedPPOCNNPopulation))
     deepq = args.agent_alias == "deep-q"
     history = {"writer": writer, "t": 0, "t_learn": 0}
     period = 0
@@ -293,7 +294,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
 
 def members_n_envs(args):
-    """--members M. ppo-mlp: the batch is N = M x rollouts envs (sets args.n_envs; an explicit -N that disagrees stops the run). deep-q:
+    """--members M. ppo-mlp, ppo-cnn: the batch is N = M x rollouts envs (sets args.n_envs; an explicit -N that disagrees stops the run). deep-q:
     the batch is -N envs, N / M per member (N must be a multiple of M). Another agent stops the run with a message."""
     members = int(args.members)
     if members < 1:
@@ -306,8 +307,8 @@ def members_n_envs(args):
         if getattr(args, "q_body", "mlp") != "mlp":
             raise SystemExit("--members runs a population of the reference's MLP deep-q agents, not --q-body %s" % args.q_body)
         return n
-    if args.agent_alias != "ppo-mlp":
-        raise SystemExit("--members runs a population of ppo-mlp or deep-q agents, not %r" % (args.agent_alias,))
+    if args.agent_alias not in ("ppo-mlp", "ppo-cnn"):
+        raise SystemExit("--members runs a population of ppo-mlp, ppo-cnn or deep-q agents, not %r" % (args.agent_alias,))
     n = members * int(args.rollouts)
     if int(getattr(args, "n_envs", 0) or 0) not in (0, n):
         raise SystemExit("--members %d with --rollouts %d is a batch of %d envs; -N %d disagrees (leave -N out)"
