@@ -537,7 +537,7 @@ SGK_API int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *lear
  *                    [n_members][n_cells][H], tb1, tw2t [n_members][H][H], tb2, tw3 [n_members][4][H], tb3 [n_members][4]; step int64
  *                    [n_members]; loss_out float [n_members] or NULL; rows / rows_out int64 [n_members][batch] or NULL.
  *   shared           the replay ring ([slices][n_envs][...], all members' env columns side by side, as sgk_step_store fills it) and
- *                    every hyper-parameter.
+ *                    the learner's hyper-parameters (lr and discount per member: sgk_dqn_sgd_step_members_hyper).
  *   rows             transitions keep their GLOBAL index slice * n_envs + env. Member m draws d uniformly from [0, slices_filled * E)
  *                    with sgk_dqn_sgd_step's Philox call (stream 4, counter (sample, 0, its own Adam step, 4)) keyed by
  *                    member_keys_dev[m] (uint64 [n_members], device; NULL: the handle's seed for every member) and trains on the
@@ -554,6 +554,21 @@ SGK_API int sgk_dqn_sgd_step_reset_store(sgk_env *h, const sgk_dqn_learner *lear
  * kernel fills a CU's LDS: the members run one per CU, and in waves above one member per CU.
  * sgk_dqn_members_workspace_bytes: -1 (and sgk_last_error) for a shape without a kernel. */
 SGK_API int64_t sgk_dqn_members_workspace_bytes(sgk_env *h, int32_t n_hidden, int32_t n_members);
+/* One member's hyper-parameters for sgk_dqn_sgd_step_members_hyper, as they lie in device memory. */
+typedef struct sgk_dqn_member_hyper {
+  double lr, discount;
+} sgk_dqn_member_hyper;
+/* sgk_dqn_sgd_step_members with ONE lr AND ONE discount PER MEMBER: hyper_dev is sgk_dqn_member_hyper [n_members] in device memory;
+ * workgroup m of the SGD kernel loads its element once at entry and converts each field with the (float) cast the host applies to
+ * learner->lr / learner->discount, then uses the results where the shared call uses those (Adam's step size, the target
+ * r + discount * max Q'). learner->lr and learner->discount are ignored; beta1, beta2, eps, max_grad_norm stay the learner's. With
+ * every element {learner->lr, learner->discount} the call leaves the bytes sgk_dqn_sgd_step_members leaves. The values are read when
+ * the kernel runs: a recorded call follows what is copied into the array between replays. The member instantiation of the kernels
+ * is used for every n_members, 1 included. SGK_ERR_INVALID for hyper_dev == NULL and whatever sgk_dqn_sgd_step_members refuses, for
+ * the same reason. The contents are not validated (the caller keeps them finite, lr > 0, 0 < discount <= 1). No allocation, no host
+ * synchronisation. */
+SGK_API int sgk_dqn_sgd_step_members_hyper(sgk_env *h, const sgk_dqn_learner *learner, int32_t n_members, const uint64_t *member_keys_dev,
+                                           void *workspace, const sgk_dqn_member_hyper *hyper_dev);
 SGK_API int sgk_dqn_sgd_step_members(sgk_env *h, const sgk_dqn_learner *learner, int32_t n_members, const uint64_t *member_keys_dev,
                                      void *workspace);
 
@@ -601,10 +616,25 @@ SGK_API int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *learner);
  * shared: n_trajectories = all members' trajectories (sgk_policy_rollout_members' outputs), rows are global (step * n_trajectories +
  * trajectory) and member m draws its own from its own trajectories -- the trajectory from [0, E) by sgk_ppo_epochs' Philox call, then
  * offset by m * E -- keyed by member_keys_dev[m] (uint64 [n_members], device) and its own Adam step; member_keys_dev NULL: the handle's
- * seed for every member. All hyper-parameters are shared. n_members = 1 with member_keys_dev NULL IS sgk_ppo_epochs (the same kernel).
+ * seed for every member. All hyper-parameters are the learner's (one set per member: sgk_ppo_epochs_members_hyper). n_members = 1 with member_keys_dev NULL IS sgk_ppo_epochs (the same kernel).
  * SGK_ERR_INVALID for n_members < 1, n_trajectories % n_members != 0 and whatever sgk_ppo_epochs refuses. No allocation, no host
  * synchronisation: can be recorded in a graph. A workgroup fills a CU's LDS: up to one member per CU runs at a time. */
 SGK_API int sgk_ppo_epochs_members(sgk_env *h, const sgk_ppo_learner *learner, int32_t n_members, const uint64_t *member_keys_dev);
+/* One member's hyper-parameters for sgk_ppo_epochs_members_hyper / sgk_ppo_cnn_epochs_members_hyper, as they lie in device memory. */
+typedef struct sgk_ppo_member_hyper {
+  double lr, clipping, critic_coeff, entropy_bonus;
+} sgk_ppo_member_hyper;
+/* sgk_ppo_epochs_members with ONE lr, clipping, critic_coeff AND entropy_bonus PER MEMBER: hyper_dev is sgk_ppo_member_hyper
+ * [n_members] in device memory; workgroup m loads its element once at entry, converts each field with the (float) cast the host applies
+ * to the learner's four fields, and uses the results wherever the shared call uses those. The learner's four fields are ignored;
+ * beta1, beta2 and eps stay the learner's. Member m is the reference's run with its own hyper-parameters on its own trajectories: with
+ * every element equal to the learner's fields the call leaves the bytes sgk_ppo_epochs_members leaves. The values are read when the
+ * kernel runs: a recorded call follows what is copied into the array between replays. SGK_ERR_INVALID for hyper_dev == NULL and
+ * whatever sgk_ppo_epochs_members refuses, for the same reason. The contents are not validated (the caller keeps them finite and
+ * lr > 0). No allocation, no host synchronisation. (The per-member discount of a PPO member is in its returns:
+ * sgk_discounted_returns_members.) */
+SGK_API int sgk_ppo_epochs_members_hyper(sgk_env *h, const sgk_ppo_learner *learner, int32_t n_members, const uint64_t *member_keys_dev,
+                                         const sgk_ppo_member_hyper *hyper_dev);
 /* ---- PPOBaseAgent.learn (reference policy_base.py:64-131) for PPOCNNAgent (policy_cnn.py:17-81) on the device ------------ */
 /* All `n_epochs` minibatch updates of one learn() call, three launches per epoch enqueued by this one call (forward, backward, Adam;
  * no allocation, no host synchronisation, no float atomics: deterministic, and a captured replay equals the eager call bit for bit).
@@ -662,7 +692,7 @@ SGK_API int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int3
  * member_keys_dev[m] (uint64 [n_members], device; NULL: the handle's seed for every member) and its OWN step counter, then offsets it
  * by m * E. A caller's row outside the rollout, or of a trajectory that is not member m's own, trains on the member's first row (step
  * 0, trajectory m * E). The backward kernel forms the advantage statistics from its own member's samples only. All hyper-parameters
- * are shared. The member instantiation of the kernels is used for every n_members, 1 included (where, with member_keys_dev NULL and
+ * are the learner's (one set per member: sgk_ppo_cnn_epochs_members_hyper). The member instantiation of the kernels is used for every n_members, 1 included (where, with member_keys_dev NULL and
  * valid rows, it leaves the bytes sgk_ppo_cnn_epochs leaves). No allocation, no host synchronisation, no atomics: can be recorded in
  * a graph. SGK_ERR_INVALID for n_members outside 1 .. 65535, n_trajectories % n_members != 0, a NULL or misaligned workspace and
  * whatever sgk_ppo_cnn_epochs refuses. */
@@ -670,6 +700,13 @@ SGK_API int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *le
 /* The workspace sgk_ppo_cnn_epochs_members needs, in bytes; -1 (sgk_last_error says why) for n_members < 1 or an unsupported
  * n_channels, board shape or batch. */
 SGK_API int64_t sgk_ppo_cnn_members_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch, int32_t n_members);
+/* sgk_ppo_cnn_epochs_members with sgk_ppo_epochs_members_hyper's per-member values: hyper_dev is sgk_ppo_member_hyper [n_members] in
+ * device memory; the member coordinate of the backward launch loads clipping, critic_coeff and entropy_bonus, that of the Adam launch lr,
+ * each converted with the host's (float) cast (the forward launch reads none of them). Equal values leave sgk_ppo_cnn_epochs_members'
+ * bytes; read at run time, so a recorded call follows the array. SGK_ERR_INVALID for hyper_dev == NULL and whatever
+ * sgk_ppo_cnn_epochs_members refuses, for the same reason. No allocation, no host synchronisation. */
+SGK_API int sgk_ppo_cnn_epochs_members_hyper(sgk_env *h, const sgk_ppo_cnn_learner *learner, int32_t n_members,
+                                             const uint64_t *member_keys_dev, const sgk_ppo_member_hyper *hyper_dev);
 /* ReplayBuffer.add for every env (reference contain.py:15-17 via value.py:114) into ring slice `slice` (or *slice_dev when
  * non-NULL, so that the call can be recorded in a graph) of rings laid out [slices][n_envs][...]: phase 0, called before
  * sgk_step, stores the current boards as the transitions' state; phase 1, called after it, stores the boards as successor
@@ -719,6 +756,19 @@ SGK_API int sgk_policy_rollout_members(sgk_env *h, const sgk_mlp_weights *w, int
                                        uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev,
                                        uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev);
 
+/* sgk_policy_rollout_members with ONE EPSILON PER MEMBER: member_epsilon_dev is double [n_members] in device memory, and in mode 0
+ * member m's envs draw with member_epsilon_dev[m] where sgk_policy_rollout_members uses `epsilon`. The workgroup loads its member's value
+ * once (it serves one member for the whole launch) and hands the double to the same conversion and comparison as the scalar path, so
+ * equal values give equal actions: with every element equal to `epsilon` the call leaves the bytes sgk_policy_rollout_members leaves.
+ * The value is read when the kernel runs: a recorded launch follows what the caller copies into the array between replays. Mode 1
+ * ignores the array (and `epsilon`, as before). `epsilon` itself is unused in mode 0. SGK_ERR_INVALID for member_epsilon_dev == NULL
+ * and whatever sgk_policy_rollout_members refuses, for the same reason. The contents are not validated (the caller keeps 0 <= eps <= 1).
+ * No allocation, no host synchronisation. */
+SGK_API int sgk_policy_rollout_members_eps(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                                           uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev,
+                                           uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev,
+                                           const double *member_epsilon_dev);
+
 /* ---- PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186), batched ------------------------------ */
 /* rewards_dev / returns_dev: float32 [n_trajectories][t_max] row-major; lengths_dev: int32 [n_trajectories] or NULL
  * (every trajectory t_max long). returns[i][t] = sum_{k >= t} float32(discount ** k) * rewards[i][k], accumulated left
@@ -726,6 +776,18 @@ SGK_API int sgk_policy_rollout_members(sgk_env *h, const sgk_mlp_weights *w, int
  * t_max <= 1024. Runs on the handle's stream. */
 SGK_API int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
                                    int64_t n_trajectories, int32_t t_max, double discount);
+
+/* The table behind sgk_discounted_returns, on the host: out_host[t] = (float)pow(discount, t) for t < t_max (Python's float ** int,
+ * then float32). 1 <= t_max <= 1024; no handle, no device. */
+SGK_API int sgk_discount_powers(double discount, int32_t t_max, float *out_host);
+/* sgk_discounted_returns' scan with ONE DISCOUNT PER MEMBER: trajectory i reads row i / E, E = n_trajectories / n_members, of the
+ * CALLER's table gamma_pow_dev, float32 [n_members][t_max] in device memory, each row filled as sgk_discount_powers fills it (t_max of
+ * the table == t_max of the call). With every row that of `discount` the returns are sgk_discounted_returns' bytes. Unlike that call
+ * -- which keeps one table per handle and synchronises the host twice whenever the discount changes -- this one allocates nothing,
+ * never synchronises and can be recorded in a graph; it reads the table when the kernel runs. SGK_ERR_INVALID for a NULL table,
+ * n_members < 1, n_trajectories % n_members != 0 and whatever sgk_discounted_returns refuses. */
+SGK_API int sgk_discounted_returns_members(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
+                                           int64_t n_trajectories, int32_t t_max, int32_t n_members, const float *gamma_pow_dev);
 
 /* What one unit of the integer rewards (step records, episode sums, the metrics vector's sums and maxima) is worth: 1.0, except
  * TomatoWatering's REWARD_FACTOR = 0.02 per watered tomato (the reference consumes the float: learn.py:38-48, meters.py:76-84).

@@ -814,7 +814,7 @@ int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t draw_index,
 // sgk_policy_rollout (one member) and sgk_policy_rollout_members: the same checks, the same kernel
 static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon, uint64_t draw_index0,
                                int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
-                               sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) {
+                               sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev, const double *member_epsilon_dev = nullptr) {
   SGK_CHECK_HANDLE(h);
   if (!w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3) return fail(SGK_ERR_INVALID, "NULL argument");
   if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
@@ -831,7 +831,8 @@ static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_m
   sgk::Shard &s = h->sh;
   sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
   SGK_HIP(sgk::launch_policy_rollout(s, mode, pw, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev,
-                                     reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev));
+                                     reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev,
+                                     member_epsilon_dev));
   SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
   s.lockstep_t += (uint64_t)n_steps;
   h->t_dev_stale = true;
@@ -849,6 +850,16 @@ int sgk_policy_rollout_members(sgk_env *h, const sgk_mlp_weights *w, int32_t n_m
                                sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev) try {
   return policy_rollout_impl(h, w, n_members, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev,
                              member_metrics_dev);
+} SGK_CATCH_STATUS
+
+int sgk_policy_rollout_members_eps(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon,
+                                   uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
+                                   sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev, const double *member_epsilon_dev) try {
+  // (the pointer first: the refusal needs no handle and no device)
+  if (!member_epsilon_dev)
+    return fail(SGK_ERR_INVALID, "member_epsilon_dev is NULL: sgk_policy_rollout_members_eps reads one epsilon per member from device memory");
+  return policy_rollout_impl(h, w, n_members, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev, recs_out_dev,
+                             member_metrics_dev, member_epsilon_dev);
 } SGK_CATCH_STATUS
 
 int sgk_replay_store(sgk_env *h, int32_t phase, const uint8_t *actions_dev, int32_t cheat, int64_t slice, const int64_t *slice_dev,
@@ -971,7 +982,11 @@ struct DqnMembers {  // sgk_dqn_sgd_step_members' own arguments
   int32_t n_members;
   const uint64_t *keys;
   void *workspace;
+  const sgk_dqn_member_hyper *hyper = nullptr;  // sgk_dqn_sgd_step_members_hyper's
 };
+static_assert(sizeof(sgk_dqn_member_hyper) == sizeof(sgk::DqnMemberHyper) && sizeof(sgk_dqn_member_hyper) == 2 * sizeof(double) &&
+                  sizeof(sgk_ppo_member_hyper) == sizeof(sgk::PpoMemberHyper) && sizeof(sgk_ppo_member_hyper) == 4 * sizeof(double),
+              "the per-member hyper-parameter structs are plain doubles, the kernels' own layout");
 
 static bool dqn_shape_has_kernel(int n_cells, int n_hidden) {
   return sgk::mlp_cells_have_kernel(n_cells) && (n_hidden == 64 || n_hidden == 100);
@@ -1030,6 +1045,7 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
   if (mem) {  // the two-launch form on the caller's workspace: no allocation, nothing of the handle's
     d.n_members = mem->n_members;
     d.member_keys = mem->keys;
+    d.member_hyper = reinterpret_cast<const sgk::DqnMemberHyper *>(mem->hyper);
     d.scratch = mem->workspace;
     d.scratch_stride = sgk::dqn_members_scratch_stride(h->sh.n_cells, L->n_hidden);
   } else if (!one_launch || rs) {
@@ -1084,8 +1100,18 @@ int sgk_dqn_sgd_step_members(sgk_env *h, const sgk_dqn_learner *L, int32_t n_mem
   return dqn_sgd_step_impl(h, L, nullptr, &mem);
 } SGK_CATCH_STATUS
 
-// sgk_ppo_epochs (one member, the handle's seed) and sgk_ppo_epochs_members: the same checks, the same kernel
-static int ppo_epochs_impl(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev) {
+int sgk_dqn_sgd_step_members_hyper(sgk_env *h, const sgk_dqn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                                   void *workspace, const sgk_dqn_member_hyper *hyper_dev) try {
+  // (the pointer first: the refusal needs no handle and no device)
+  if (!hyper_dev)
+    return fail(SGK_ERR_INVALID, "hyper_dev is NULL: sgk_dqn_sgd_step_members_hyper reads one {lr, discount} per member from device memory");
+  const DqnMembers mem{n_members, member_keys_dev, workspace, hyper_dev};
+  return dqn_sgd_step_impl(h, L, nullptr, &mem);
+} SGK_CATCH_STATUS
+
+// sgk_ppo_epochs (one member, the handle's seed), sgk_ppo_epochs_members and sgk_ppo_epochs_members_hyper: the same checks, the same kernel
+static int ppo_epochs_impl(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                           const sgk_ppo_member_hyper *hyper_dev = nullptr) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
   const void *need[] = {L->states, L->actions, L->returns, L->lengths, L->w1, L->b1, L->w2, L->b2, L->wa, L->ba, L->wc, L->bc,
@@ -1118,7 +1144,8 @@ static int ppo_epochs_impl(sgk_env *h, const sgk_ppo_learner *L, int32_t n_membe
   d.rows_out = reinterpret_cast<long long *>(L->rows_out);
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
   d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
-  SGK_HIP(sgk::launch_ppo_epochs(h->sh, d, h->stream, n_members, member_keys_dev));
+  SGK_HIP(sgk::launch_ppo_epochs(h->sh, d, h->stream, n_members, member_keys_dev,
+                                 reinterpret_cast<const sgk::PpoMemberHyper *>(hyper_dev)));
   return SGK_OK;
 }
 
@@ -1126,6 +1153,15 @@ int sgk_ppo_epochs(sgk_env *h, const sgk_ppo_learner *L) try { return ppo_epochs
 
 int sgk_ppo_epochs_members(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev) try {
   return ppo_epochs_impl(h, L, n_members, member_keys_dev);
+} SGK_CATCH_STATUS
+
+int sgk_ppo_epochs_members_hyper(sgk_env *h, const sgk_ppo_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                                 const sgk_ppo_member_hyper *hyper_dev) try {
+  // (the pointer first: the refusal needs no handle and no device)
+  if (!hyper_dev)
+    return fail(SGK_ERR_INVALID, "hyper_dev is NULL: sgk_ppo_epochs_members_hyper reads one {lr, clipping, critic_coeff, entropy_bonus} per "
+                                 "member from device memory");
+  return ppo_epochs_impl(h, L, n_members, member_keys_dev, hyper_dev);
 } SGK_CATCH_STATUS
 
 int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch) try {
@@ -1152,7 +1188,8 @@ int64_t sgk_ppo_cnn_members_workspace_bytes(sgk_env *h, int32_t n_channels, int3
 } SGK_CATCH_VALUE(-1)
 
 // sgk_ppo_cnn_epochs (n_members 0: its own kernels, the handle's seed) and sgk_ppo_cnn_epochs_members: the same checks
-static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev) {
+static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                               const sgk_ppo_member_hyper *hyper_dev = nullptr) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
   if (!L->workspace && n_members > 0)
@@ -1183,13 +1220,16 @@ static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t
   d.workspace = L->workspace;
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
   d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
-  SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream, n_members, member_keys_dev));
+  SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream, n_members, member_keys_dev,
+                                     reinterpret_cast<const sgk::PpoMemberHyper *>(hyper_dev)));
   return SGK_OK;
 }
 
 int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try { return ppo_cnn_epochs_impl(h, L, 0, nullptr); } SGK_CATCH_STATUS
 
-int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev) try {
+// sgk_ppo_cnn_epochs_members' own checks, then the shared ones (hyper_dev: sgk_ppo_cnn_epochs_members_hyper's)
+static int ppo_cnn_epochs_members_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                                       const sgk_ppo_member_hyper *hyper_dev) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
   if (n_members < 1 || n_members > 65535) return fail(SGK_ERR_INVALID, "n_members must be in 1 .. 65535 (got %d)", (int)n_members);
@@ -1197,7 +1237,20 @@ int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t
     return fail(SGK_ERR_INVALID, "n_trajectories (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
                 (long long)L->n_trajectories, (int)n_members);
   if ((uintptr_t)L->workspace & 7u) return fail(SGK_ERR_INVALID, "workspace must be 8-byte aligned");
-  return ppo_cnn_epochs_impl(h, L, n_members, member_keys_dev);
+  return ppo_cnn_epochs_impl(h, L, n_members, member_keys_dev, hyper_dev);
+}
+
+int sgk_ppo_cnn_epochs_members(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev) try {
+  return ppo_cnn_epochs_members_impl(h, L, n_members, member_keys_dev, nullptr);
+} SGK_CATCH_STATUS
+
+int sgk_ppo_cnn_epochs_members_hyper(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
+                                     const sgk_ppo_member_hyper *hyper_dev) try {
+  // (the pointer first: the refusal needs no handle and no device)
+  if (!hyper_dev)
+    return fail(SGK_ERR_INVALID, "hyper_dev is NULL: sgk_ppo_cnn_epochs_members_hyper reads one {lr, clipping, critic_coeff, entropy_bonus} "
+                                 "per member from device memory");
+  return ppo_cnn_epochs_members_impl(h, L, n_members, member_keys_dev, hyper_dev);
 } SGK_CATCH_STATUS
 
 int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
@@ -1209,7 +1262,7 @@ int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *
   if (!h->gamma_dev) SGK_HIP(hipMalloc(&h->gamma_dev, sizeof(float) * 1024));
   if (h->gamma_discount != discount) {
     float tab[1024];
-    for (int t = 0; t < 1024; ++t) tab[t] = (float)std::pow(discount, (double)t);  // Python: float ** int, then float32
+    sgk::host::discount_powers(discount, 1024, tab);
     SGK_HIP(sgk::host::wait_stream(h->stream));  // a previous launch may still read the old table
     SGK_HIP(hipMemcpyAsync(h->gamma_dev, tab, sizeof(tab), hipMemcpyHostToDevice, h->stream));  // (not hipMemcpy: sgk::capture_mutex)
     SGK_HIP(sgk::host::wait_stream(h->stream));  // `tab` is on the stack
@@ -1217,6 +1270,30 @@ int sgk_discounted_returns(sgk_env *h, const float *rewards_dev, const int32_t *
   }
   SGK_HIP(sgk::launch_discounted_returns(h->sh, rewards_dev, lengths_dev, h->gamma_dev, returns_dev, n_trajectories, t_max,
                                          h->stream));
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
+int sgk_discount_powers(double discount, int32_t t_max, float *out_host) try {
+  if (!out_host) return fail(SGK_ERR_INVALID, "out_host is NULL");
+  if (t_max < 1 || t_max > 1024) return fail(SGK_ERR_INVALID, "t_max must be in 1..1024");
+  sgk::host::discount_powers(discount, t_max, out_host);
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
+int sgk_discounted_returns_members(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
+                                   int64_t n_trajectories, int32_t t_max, int32_t n_members, const float *gamma_pow_dev) try {
+  if (!gamma_pow_dev)  // (the pointer first: the refusal needs no handle and no device)
+    return fail(SGK_ERR_INVALID, "gamma_pow_dev is NULL: sgk_discounted_returns_members reads the caller's table [n_members][t_max]");
+  SGK_CHECK_HANDLE(h);
+  if (!rewards_dev || !returns_dev) return fail(SGK_ERR_INVALID, "NULL argument");
+  if (n_trajectories < 0 || t_max < 1 || t_max > 1024) return fail(SGK_ERR_INVALID, "t_max must be in 1..1024");
+  if (n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)n_members);
+  if (n_trajectories % n_members != 0)
+    return fail(SGK_ERR_INVALID, "n_trajectories (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
+                (long long)n_trajectories, (int)n_members);
+  if (n_trajectories == 0) return SGK_OK;
+  SGK_HIP(sgk::launch_discounted_returns(h->sh, rewards_dev, lengths_dev, gamma_pow_dev, returns_dev, n_trajectories, t_max, h->stream,
+                                         n_trajectories / n_members));
   return SGK_OK;
 } SGK_CATCH_STATUS
 

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -201,6 +202,12 @@ inline StreamPool &stream_pool() {
 // thread's handle recorded its step graph, 2 failures in 17 runs of the suite). The library itself no longer makes such calls on a
 // handle's path (uploads go through the handle's stream); sgk_ring_free's device synchronisation takes this mutex, and so does
 // every capture. A capture invalidated by somebody else's synchronous call (the caller's own, PyTorch's) is retried.
+// the discounted-returns table: out[t] = float32(discount ** t), Python's float ** int rounded to float32 (policy_base.py:179-186).
+// ONE definition for sgk_discounted_returns' own table and sgk_discount_powers (the rows of sgk_discounted_returns_members' table)
+inline void discount_powers(double discount, int t_max, float *out) {
+  for (int t = 0; t < t_max; ++t) out[t] = (float)std::pow(discount, (double)t);
+}
+
 inline std::mutex &capture_mutex() {
   static std::mutex m;
   return m;

@@ -88,9 +88,10 @@ hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, 
 // n_steps of {forward, draw, env.step} in one launch; trajectory outputs optional ([n_steps][n]...); SGK_F_AUTO_RESET in flags.
 // n_members > 1: `w` addresses member 0 of weight tensors stacked [n_members][...], member m acts in the envs m * n / n_members ..;
 // member_metrics: int64 [n_members][SGK_METRICS_LEN] each member's episodes are also booked in, or null
+// member_eps (mode 0): double [n_members] on the device, member m's epsilon instead of `eps`; null: `eps` for every member
 hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights &w, double eps, uint64_t draw0, int32_t n_steps,
                                  uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
-                                 int n_members = 1, int64_t *member_metrics = nullptr);
+                                 int n_members = 1, int64_t *member_metrics = nullptr, const double *member_eps = nullptr);
 hipError_t launch_eps_greedy(const Shard &sh, int mode, const float *scores, uint8_t *actions, double eps, uint64_t draw,
                              const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
 // the conv Q-body's forward + act_explore in one launch (sgk_convq.hip; a labelled NON-parity option: the reference's DeepQAgent is an MLP)
@@ -110,6 +111,13 @@ hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channe
 hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0, int32_t n_steps,
                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
                                 int n_members = 0, int64_t *member_metrics = nullptr);
+// one member's hyper-parameters in device memory: the layouts of sgk_ppo_member_hyper / sgk_dqn_member_hyper (sgk.h; sgk_api.hip checks)
+struct PpoMemberHyper {
+  double lr, clipping, critic_coeff, entropy_bonus;
+};
+struct DqnMemberHyper {
+  double lr, discount;
+};
 // DeepQAgent.learn as one kernel (sgk_learn.hip); all pointers are device pointers
 struct DqnLearner {
   const int8_t *states, *successors;
@@ -142,6 +150,8 @@ struct DqnLearner {
   int n_members = 1;
   const uint64_t *member_keys = nullptr;
   size_t scratch_stride = 0;
+  // sgk_dqn_sgd_step_members_hyper: [n_members] on the device, member m's lr and discount instead of the two above; null: shared
+  const DqnMemberHyper *member_hyper = nullptr;
 };  // (the replay's int8 rewards are in units of the level's reward_scale: launch_dqn_sgd takes it from the shard's rules)
 // env.step + the second half of ReplayBuffer.add / reset_done + the first half for the next step, one launch each (sgk_step.hip)
 hipError_t launch_step_store(const Shard &sh, const uint8_t *actions, uint32_t flags, int cheat, int64_t slice, const long long *slice_dev,
@@ -175,8 +185,9 @@ struct PpoLearner {
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden);
 // n_members > 1: one workgroup per member; every tensor of P but the rollout is stacked [n_members][...] and P addresses member 0;
 // member m draws its rows from the trajectories m * n_trajectories / n_members .. with the key member_keys[m] (null: the shard's seed)
+// member_hyper: [n_members] on the device, member m's lr / clipping / critic_coeff / entropy_bonus instead of P's; null: P's for all
 hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members = 1,
-                             const uint64_t *member_keys = nullptr);
+                             const uint64_t *member_keys = nullptr, const PpoMemberHyper *member_hyper = nullptr);
 // PPOBaseAgent.learn for PPOCNNAgent (sgk_ppo_cnn.hip): tensors in registration order (network.0.0, network.1.0.0, bottleneck,
 // actor_cnn.0, actor_linear, critic_cnn.0, critic_linear; weight then bias), the old policy's first ten
 struct PpoCnnLearner {
@@ -202,10 +213,12 @@ size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int b
 // member axis on the grid. Every tensor of P but the rollout is stacked [n_members][...] and P addresses member 0, the workspace is
 // n_members slices of ppo_cnn_members_stride_bytes(); member m draws its rows from the trajectories m * n_trajectories / n_members .. with the
 // key member_keys[m] (null: the shard's seed) and its own step counter
+// member_hyper (with n_members >= 1): as for launch_ppo_epochs, read by the backward and Adam launches
 hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members = 0,
-                                 const uint64_t *member_keys = nullptr);
+                                 const uint64_t *member_keys = nullptr, const PpoMemberHyper *member_hyper = nullptr);
+// member_envs > 0: gamma_pow is a table [n / member_envs][t_max] and trajectory i reads row i / member_envs; 0: one row for all
 hipError_t launch_discounted_returns(const Shard &sh, const float *rewards, const int32_t *lengths, const float *gamma_pow,
-                                     float *returns, int64_t n, int t_max, hipStream_t st);
+                                     float *returns, int64_t n, int t_max, hipStream_t st, int64_t member_envs = 0);
 hipError_t launch_render_rgb(const Shard &sh, uint8_t *dst, hipStream_t st);
 hipError_t launch_dense_boards(const Shard &sh, int8_t *dst, hipStream_t st);
 hipError_t launch_finished(const Shard &sh, int32_t *ids, int32_t *ret, int32_t *perf, hipStream_t st);

@@ -65,6 +65,8 @@ struct LearnArgs {
   int64_t member_envs, member_total;  // E = n_envs / n_members; the draw's range, filled slices * E
   const uint64_t *member_keys;        // [n_members] Philox keys of the members' draws; null: `seed` for every member
   int64_t scratch_stride;             // floats between two members' slices of adam_scratch
+  // sgk_dqn_sgd_step_members_hyper (the HYPER instantiation only): [n_members], member m's lr and discount instead of the two above
+  const DqnMemberHyper *member_hyper;
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -390,8 +392,17 @@ struct AdamHeader {
 
 // MEMBERS = false is the launch of one workgroup (sgk_dqn_sgd_step, and sgk_dqn_sgd_step_members with one member): the member index is
 // the constant 0 and every offset below folds away; MEMBERS = true is the same code with workgroup m serving member m.
-template <int K0, int H, bool MEMBERS = false>
+// HYPER = true (sgk_dqn_sgd_step_members_hyper; with MEMBERS only) is MEMBERS = true with a.lr and a.discount replaced by member m's
+// element of a.member_hyper, converted with the host's (float) cast: one 16-byte load at entry, requested in front of the gather and
+// consumed behind it by the lane that forms the bias corrections -- every lane requests the same 16 bytes into VECTOR registers (the
+// index is laundered): the kernel sits at the SGPR limit, and the same load into scalar registers made the compiler reload kernel
+// arguments in front of the gather's requests (+1.0 us per call from a kernel trace), while requested where it is used it was one more
+// exposed round trip (+0.3 .. 0.8 us). As it stands the instantiation costs +0.6 .. 0.75 us against MEMBERS alone (29.8 against 29.1 us
+// at 16 members: profiles/member_hyper/new_vs_old.log). The discount is parked in LDS until the loss reads it: no register lives
+// across the forward passes for it.
+template <int K0, int H, bool MEMBERS = false, bool HYPER = false>
 __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
+  static_assert(MEMBERS || !HYPER, "per-member hyper-parameters come with the member axis");
   SGK_STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char learn_smem[];
   const int B = a.batch;
@@ -413,6 +424,12 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   // bytes a lane fetches is derived by that lane (16 lanes per sample, each the same draw): the board gather needs no exchange
   // through LDS behind the draw, so indices, scalars and both boards travel together (they were two round trips and a barrier).
   const long long step0 = a.step[mb];
+  DqnMemberHyper hp{};
+  if constexpr (HYPER) {
+    int same = 0;
+    asm volatile("" : "+v"(same));  // (a vector load: see above)
+    hp = a.member_hyper[mb + same];
+  }
   // the first weight matrix and the small tensors are independent of it: requested first, so that they are in flight meanwhile
   RowsInFlight<H, K0> first;
   rows_request<H, K0>(first, a.tw1t + mo.w1());
@@ -474,7 +491,12 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
   rows_commit<H, K0>(L.ST, first);
   if (t == LWG - 1) {  // Adam's bias corrections (two double-precision pow(), ~1.3 us on one lane) in the shadow of the gather
     const long long step = step0 + 1;
-    L.scratch[16] = a.lr / (float)(1.0 - pow((double)a.beta1, (double)step));
+    float lr = a.lr;
+    if constexpr (HYPER) {
+      lr = (float)hp.lr;
+      L.scratch[18] = (float)hp.discount;  // (block_sum uses scratch[0 .. 15], the bias corrections 16 and 17)
+    }
+    L.scratch[16] = lr / (float)(1.0 - pow((double)a.beta1, (double)step));
     L.scratch[17] = 1.0f / sqrtf((float)(1.0 - pow((double)a.beta2, (double)step)));
   }
   __syncthreads();
@@ -523,7 +545,8 @@ __global__ __launch_bounds__(LWG) void dqn_sgd_kernel(LearnArgs a) {
     float g = 0.0f, target = 0.0f, qsa = 0.0f;
     if (t < B) {
       const float nq = fmaxf(fmaxf(L.tq[t * 4], L.tq[t * 4 + 1]), fmaxf(L.tq[t * 4 + 2], L.tq[t * 4 + 3]));
-      target = a.discount * (L.term[t] ? 0.0f : nq) + L.rew[t];
+      const float discount = HYPER ? L.scratch[18] : a.discount;
+      target = discount * (L.term[t] ? 0.0f : nq) + L.rew[t];
       qsa = L.q[t * 4 + L.act[t]];
     }
     if (a.loss_mode == 0) {
@@ -885,6 +908,8 @@ struct PpoArgs {
   uint64_t seed;
   const uint64_t *member_keys;  // [n_members] Philox keys of the members' draws; null: `seed` for every member
   float lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
+  // sgk_ppo_epochs_members_hyper (the HYPER instantiation only): [n_members], member m's lr / clipping / critic_coeff / entropy_bonus
+  const PpoMemberHyper *member_hyper;
 };
 
 struct PpoLds {
@@ -949,7 +974,11 @@ __device__ __forceinline__ float adam_plain(float p, float &m, float &v, float g
   return p - c.lr_bc1 * (m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * c.inv_bc2_sqrt + c.eps));  // (one-ulp sqrt / rcp: adam_scalar)
 }
 
-template <int K0, int H>
+// HYPER = true (sgk_ppo_epochs_members_hyper): workgroup m reads lr, clipping, critic_coeff and entropy_bonus from its element of
+// a.member_hyper instead of `a`, converted with the host's (float) cast -- ONE 32-byte load at entry, where the member's offsets are
+// formed, parked in LDS (scratch[18 .. 21]: the epoch loop's first barrier publishes them) so that no register lives across the
+// epochs for them: the kernel sits at its 128-VGPR budget.
+template <int K0, int H, bool HYPER = false>
 __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char learn_smem[];
   constexpr int KP = (K0 + 3) & ~3;
@@ -973,6 +1002,13 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
     if (a.rows) a.rows += per_epoch * (size_t)a.batch;
     if (a.rows_out) a.rows_out += per_epoch * (size_t)a.batch;
     if (a.member_keys) a.seed = a.member_keys[mb];
+    if constexpr (HYPER) {
+      if (t0 == 0) {
+        const PpoMemberHyper hp = a.member_hyper[mb];
+        L.scratch[18] = (float)hp.lr; L.scratch[19] = (float)hp.clipping;
+        L.scratch[20] = (float)hp.critic_coeff; L.scratch[21] = (float)hp.entropy_bonus;
+      }
+    }
   }
   const long long traj0 = (long long)blockIdx.x * a.E;  // this member's first trajectory
   const long long step0 = *a.step;
@@ -1096,7 +1132,9 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
       const float dev = live ? adv - mu : 0.0f;
       const float sigma = sqrtf(__ockl_wfred_add_f32(dev * dev) / (float)(B - 1));
       const float advn = dev / sigma;
-      const float lo_c = 1.0f - a.clipping, hi_c = 1.0f + a.clipping;
+      const float clipping = HYPER ? L.scratch[19] : a.clipping, critic_coeff = HYPER ? L.scratch[20] : a.critic_coeff;
+      const float entropy_bonus = HYPER ? L.scratch[21] : a.entropy_bonus;
+      const float lo_c = 1.0f - clipping, hi_c = 1.0f + clipping;
       const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
       const float s1 = advn * ratio, s2 = advn * rc;
       const float w1 = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f), w2 = 1.0f - w1;  // torch.min's gradient: halves on a tie
@@ -1108,12 +1146,12 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
       const float gbar = __ockl_wfred_add_f32(g_advn) * invB;
       const float S = __ockl_wfred_add_f32(g_advn * dev);
       const float g_adv = live ? (g_advn - gbar) / sigma - dev * S / ((float)(B - 1) * sigma * sigma * sigma) : 0.0f;
-      const float dv = live ? a.critic_coeff * 2.0f * (v - r) * invB - g_adv : 0.0f;
+      const float dv = live ? critic_coeff * 2.0f * (v - r) * invB - g_adv : 0.0f;
       float dl[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float onehot = k == ac ? 1.0f : 0.0f;
-        dl[k] = live ? g_logp * (onehot - p[k]) + a.entropy_bonus * invB * p[k] * (logp[k] + ent) : 0.0f;
+        dl[k] = live ? g_logp * (onehot - p[k]) + entropy_bonus * invB * p[k] * (logp[k] + ent) : 0.0f;
       }
       *reinterpret_cast<f4 *>(L.dout + b * 8) = (f4){dl[0], dl[1], dl[2], dl[3]};
       *reinterpret_cast<f4 *>(L.dout + b * 8 + 4) = (f4){dv, 0.0f, 0.0f, 0.0f};
@@ -1156,7 +1194,7 @@ __global__ __launch_bounds__(LWG) void ppo_epochs_kernel(PpoArgs a) {
     if (epoch + 1 < a.n_epochs) draw_rows(epoch + 1, step + 1, t, lane);  // act / ret / oout are free from here on
     // ---- Adam (torch defaults: no amsgrad, no gradient clipping) ----
     if (t == 0) {
-      L.scratch[16] = a.lr / (float)(1.0 - pow((double)a.beta1, (double)(step + 1)));
+      L.scratch[16] = (HYPER ? L.scratch[18] : a.lr) / (float)(1.0 - pow((double)a.beta1, (double)(step + 1)));
       L.scratch[17] = 1.0f / sqrtf((float)(1.0 - pow((double)a.beta2, (double)(step + 1))));
     }
     __syncthreads();
@@ -1318,18 +1356,19 @@ bool mlp_cells_have_kernel(int n_cells) {
 }
 
 // the SGD kernel of one shape (the 160 KB dynamic-LDS opt-in is made on its first launch per device)
-template <int K0, int H, bool MEMBERS>
+template <int K0, int H, bool MEMBERS, bool HYPER = false>
 static hipError_t launch_sgd(const LearnArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
-  hipError_t ae = allow_dynamic_lds<dqn_sgd_kernel<K0, H, MEMBERS>>(device, 160 * 1024);
+  hipError_t ae = allow_dynamic_lds<dqn_sgd_kernel<K0, H, MEMBERS, HYPER>>(device, 160 * 1024);
   if (ae != hipSuccess) return ae;
-  dqn_sgd_kernel<K0, H, MEMBERS><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
+  dqn_sgd_kernel<K0, H, MEMBERS, HYPER><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
   return hipSuccess;
 }
 
 // one shape's launches: the SGD kernel and, with `adam`, dqn_adam_kernel behind it (the two-launch form without a fused reset)
 template <int K0, int H>
 static hipError_t launch_sgd_adam(const LearnArgs &a, int n_members, bool adam, size_t lds, int device, hipStream_t st) {
-  hipError_t se = (n_members > 1 || a.member_keys) ? launch_sgd<K0, H, true>(a, n_members, lds, device, st)
+  hipError_t se = a.member_hyper                   ? launch_sgd<K0, H, true, true>(a, n_members, lds, device, st)
+                  : (n_members > 1 || a.member_keys) ? launch_sgd<K0, H, true>(a, n_members, lds, device, st)
                                                    : launch_sgd<K0, H, false>(a, 1, lds, device, st);
   if (se != hipSuccess) return se;
   if (adam) {
@@ -1356,6 +1395,8 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
   LearnArgs a;
   a.member_envs = sh.n / n_members; a.member_total = (int64_t)L.slices_filled * a.member_envs;
   a.member_keys = L.member_keys; a.scratch_stride = (int64_t)(L.scratch_stride / sizeof(float));
+  a.member_hyper = L.member_hyper;
+  if (a.member_hyper && (!L.scratch || L.reset_store)) return hipErrorInvalidValue;  // (the members' two-launch form only)
   a.states = L.states; a.successors = L.successors; a.actions = L.actions; a.rewards = L.rewards; a.terminals = L.terminals;
   a.n_envs = sh.n; a.total = (int64_t)L.slices_filled * sh.n; a.n_cells = sh.n_cells;
   a.w1 = L.w1; a.b1 = L.b1; a.w2 = L.w2; a.b2 = L.b2; a.w3 = L.w3; a.b3 = L.b3;
@@ -1411,15 +1452,22 @@ extern "C" __attribute__((visibility("default"))) int sgk_debug_learn_stamps(uns
 
 size_t ppo_epochs_lds_bytes(int n_cells, int n_hidden) { return ppo_lds_bytes((n_cells + 3) & ~3, n_hidden); }
 
-template <int K0, int H>
-static hipError_t launch_ppo(const PpoArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
-  hipError_t ae = allow_dynamic_lds<ppo_epochs_kernel<K0, H>>(device, 160 * 1024);
+template <int K0, int H, bool HYPER>
+static hipError_t launch_ppo_kernel(const PpoArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
+  hipError_t ae = allow_dynamic_lds<ppo_epochs_kernel<K0, H, HYPER>>(device, 160 * 1024);
   if (ae != hipSuccess) return ae;
-  ppo_epochs_kernel<K0, H><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
+  ppo_epochs_kernel<K0, H, HYPER><<<dim3(n_members), dim3(LWG), lds, st>>>(a);
   return hipSuccess;
 }
 
-hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys) {
+template <int K0, int H>
+static hipError_t launch_ppo(const PpoArgs &a, int n_members, size_t lds, int device, hipStream_t st) {
+  return a.member_hyper ? launch_ppo_kernel<K0, H, true>(a, n_members, lds, device, st)
+                        : launch_ppo_kernel<K0, H, false>(a, n_members, lds, device, st);
+}
+
+hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys,
+                             const PpoMemberHyper *member_hyper) {
   (void)hipGetLastError();
   if (P.batch < 2 || P.batch > LB || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 || P.n_trajectories >= (1ll << 31))
     return hipErrorInvalidValue;
@@ -1430,6 +1478,7 @@ hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t s
   a.states = P.states; a.actions = P.actions; a.returns = P.returns; a.lengths = P.lengths;
   a.T = P.horizon; a.N = P.n_trajectories; a.E = P.n_trajectories / n_members;
   a.member_keys = member_keys;
+  a.member_hyper = member_hyper;
   a.w1 = P.w1; a.b1 = P.b1; a.w2 = P.w2; a.b2 = P.b2; a.wa = P.wa; a.ba = P.ba; a.wc = P.wc; a.bc = P.bc;
   a.w1t = P.w1t; a.w2t = P.w2t;
   for (int i = 0; i < 8; ++i) { a.m[i] = P.m[i]; a.v[i] = P.v[i]; }

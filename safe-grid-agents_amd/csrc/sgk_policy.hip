@@ -339,10 +339,14 @@ struct RolloutArgs {
   int64_t member_envs;       // envs per member (n with one member)
   int32_t member_wgs;        // workgroups per member: the grid is n_members * member_wgs
   long long *member_metrics; // [n_members][SGK_METRICS_LEN]: each member's own episode sums / counts / maxima, or null
+  const double *member_eps;  // the MEPS instantiation only (sgk_policy_rollout_members_eps): [n_members], member m's epsilon for `eps`
 };
 
-template <int ENV, int H, int MODE>
+// MEPS = true (MODE 0 only): the workgroup's member loads its own epsilon once, where its weight slices are formed -- a wave-uniform
+// load of the same double that `eps` is, so select_action compares exactly as it does for the shared value.
+template <int ENV, int H, int MODE, bool MEPS = false>
 __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a) {
+  static_assert(MODE == 0 || !MEPS, "epsilon belongs to mode 0");
   constexpr int K0 = Geom<ENV>::NC;
   typedef PolicyMfmaGeom<K0, H> G;
   constexpr int MT = G::MT, KS1 = G::KS1;
@@ -364,6 +368,7 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_rollout_kernel(RolloutArgs a)
   w.b2 += (size_t)member * H;
   w.w3t += (size_t)member * (H * 4);
   w.b3 += (size_t)member * 4;
+  if constexpr (MEPS) a.eps = a.member_eps[member];
   // weights in operand order (same arrangement as policy_mfma_kernel; staged once per launch, so plainly)
   for (int i = threadIdx.x; i < G::W1; i += PMFMA_WG) {
     const int l = i & 63, s = (i >> 6) % KS1, mt = (i >> 6) / KS1;
@@ -488,15 +493,19 @@ constexpr size_t policy_rollout_lds_bytes() {
 // One wave per trajectory: the wave stages d[] in LDS, then lane t accumulates its own suffix serially -- consecutive
 // lanes read consecutive LDS words at every iteration (conflict-free). gamma_pow[t] is computed on the host in double.
 constexpr int RET_TMAX = 1024;
+// MEMBERS = true (sgk_discounted_returns_members): gamma_pow is a table [n / member_envs][t_max] and trajectory i reads row
+// i / member_envs -- a wave-uniform row, a wave serves one trajectory at a time; false: the one row, the code as it was.
+template <bool MEMBERS>
 __global__ __launch_bounds__(WG) void discounted_returns_kernel(const float *__restrict__ rewards,
                                                                 const int32_t *__restrict__ lengths,
-                                                                const float *__restrict__ gamma_pow,
-                                                                float *__restrict__ returns, int64_t n, int t_max) {
+                                                                const float *__restrict__ gamma_pow_rows,
+                                                                float *__restrict__ returns, int64_t n, int t_max, int64_t member_envs) {
   __shared__ float d[WG / 64][RET_TMAX];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int64_t traj = (int64_t)blockIdx.x * (WG / 64) + wave; traj < n; traj += (int64_t)gridDim.x * (WG / 64)) {
     const int len = lengths ? min(lengths[traj], t_max) : t_max;
     const float *r = rewards + traj * t_max;
+    const float *gamma_pow = MEMBERS ? gamma_pow_rows + (traj / member_envs) * t_max : gamma_pow_rows;
     for (int t = lane; t < len; t += 64) d[wave][t] = __fmul_rn(gamma_pow[t], r[t]);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed
@@ -559,20 +568,21 @@ hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, 
   return hipGetLastError();
 }
 
-template <int E, int HID, int MODE>
+template <int E, int HID, int MODE, bool MEPS = false>
 static hipError_t launch_rollout(const RolloutArgs &a, int grid, int device, hipStream_t st) {
   constexpr size_t lds = policy_rollout_lds_bytes<E, HID>();
-  hipError_t ae = allow_dynamic_lds<policy_rollout_kernel<E, HID, MODE>>(device, (int)lds);
+  hipError_t ae = allow_dynamic_lds<policy_rollout_kernel<E, HID, MODE, MEPS>>(device, (int)lds);
   if (ae != hipSuccess) return ae;
-  policy_rollout_kernel<E, HID, MODE><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(a);
+  policy_rollout_kernel<E, HID, MODE, MEPS><<<dim3(grid), dim3(PMFMA_WG), lds, st>>>(a);
   return hipSuccess;
 }
 
 hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights &w, double eps, uint64_t draw0, int32_t n_steps,
                                  uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
-                                 int n_members, int64_t *member_metrics) {
+                                 int n_members, int64_t *member_metrics, const double *member_eps) {
   (void)hipGetLastError();
   if (n_members < 1 || sh.n % n_members != 0) return hipErrorInvalidValue;
+  if (mode != 0) member_eps = nullptr;  // (mode 1 draws from the logits: no epsilon)
   RolloutArgs a;
   a.env = make_step_args(sh, nullptr, flags);
   a.w = w;
@@ -586,10 +596,12 @@ hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights 
   // a member's workgroups: one per tile while all members' fit the CUs (one member: exactly the shared-policy grid), at least one
   a.member_wgs = grid_for((a.member_envs + PMFMA_ENVS - 1) / PMFMA_ENVS, std::max(sh.n_cus / n_members, 1));
   a.member_metrics = reinterpret_cast<long long *>(member_metrics);
+  a.member_eps = member_eps;
   const int grid = n_members * a.member_wgs;
   hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
-#define SGK_ROLLOUT_LAUNCH(HID) \
-  (mode == 0 ? launch_rollout<E, HID, 0>(a, grid, sh.device, st) : launch_rollout<E, HID, 1>(a, grid, sh.device, st))
+#define SGK_ROLLOUT_LAUNCH(HID)                                                                                \
+  (member_eps ? launch_rollout<E, HID, 0, true>(a, grid, sh.device, st)                                        \
+              : mode == 0 ? launch_rollout<E, HID, 0>(a, grid, sh.device, st) : launch_rollout<E, HID, 1>(a, grid, sh.device, st))
   SGK_DISPATCH_ENV(sh.env_id, {
     switch (w.n_hidden) {
     case 64: le = SGK_ROLLOUT_LAUNCH(64); break;
@@ -603,10 +615,13 @@ hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights 
 }
 
 hipError_t launch_discounted_returns(const Shard &sh, const float *rewards, const int32_t *lengths, const float *gamma_pow,
-                                     float *returns, int64_t n, int t_max, hipStream_t st) {
+                                     float *returns, int64_t n, int t_max, hipStream_t st, int64_t member_envs) {
   (void)hipGetLastError();  // drop a stale error another HIP user of this thread may have left
   int grid = grid_for((n + (WG / 64) - 1) / (WG / 64), sh.max_grid * 2);
-  hipLaunchKernelGGL(discounted_returns_kernel, dim3(grid), dim3(WG), 0, st, rewards, lengths, gamma_pow, returns, n, t_max);
+  if (member_envs > 0)
+    discounted_returns_kernel<true><<<dim3(grid), dim3(WG), 0, st>>>(rewards, lengths, gamma_pow, returns, n, t_max, member_envs);
+  else
+    discounted_returns_kernel<false><<<dim3(grid), dim3(WG), 0, st>>>(rewards, lengths, gamma_pow, returns, n, t_max, (int64_t)0);
   return hipGetLastError();
 }
 

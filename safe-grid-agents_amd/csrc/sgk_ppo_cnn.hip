@@ -92,6 +92,9 @@ struct PpoCnnArgs {
   const uint64_t *member_keys;
   size_t ws_stride;
   int32_t n_epochs;
+  // the HYPER instantiations only (sgk_ppo_cnn_epochs_members_hyper): [n_members], member m's lr / clipping / critic_coeff /
+  // entropy_bonus instead of the four above
+  const PpoMemberHyper *member_hyper;
 };
 
 // this workgroup's member (0 without the member axis) and what it owns
@@ -324,14 +327,21 @@ __device__ __forceinline__ void pc_input_grad(const float *act, int g_plane, con
   }
 }
 
-template <int HH, int WW, int C, bool MEMBERS>
+// HYPER = true (with MEMBERS; sgk_ppo_cnn_epochs_members_hyper): the member coordinate loads its element of a.member_hyper once at
+// entry -- a wave-uniform load -- and converts each field with the host's (float) cast. The forward kernel reads none of the four.
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
 __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, int epoch) {
+  static_assert(MEMBERS || !HYPER, "per-member hyper-parameters come with the member axis");
   typedef PcGeom<HH, WW, C> G;
   __shared__ __attribute__((aligned(16))) float act[G::BWD_PLANES * G::PL];
   __shared__ __attribute__((aligned(16))) float w[G::P];
   __shared__ float dout[8];
   const int b = blockIdx.x, t = threadIdx.x, B = a.batch;
   const size_t mem = pc_member<MEMBERS>();
+  if constexpr (HYPER) {
+    const PpoMemberHyper hp = a.member_hyper[mem];
+    a.clipping = (float)hp.clipping; a.critic_coeff = (float)hp.critic_coeff; a.entropy_bonus = (float)hp.entropy_bonus;
+  }
   float *ws = pc_ws<MEMBERS>(a);
   const float *scal = ws + PC_HDR;  // this member's own samples
   for (int i = t; i < G::BWD_PLANES * G::PL; i += PC_WG) act[i] = 0.0f;
@@ -459,11 +469,13 @@ __device__ __forceinline__ float pc_adam(float p, float &m, float &v, float g, f
   return p - lr_bc1 * (m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * inv_bc2_sqrt + eps));  // (sgk_ppo_epochs' adam_plain)
 }
 
-template <int HH, int WW, int C, bool MEMBERS>
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
 __global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(PpoCnnArgs a) {
+  static_assert(MEMBERS || !HYPER, "per-member hyper-parameters come with the member axis");
   typedef PcGeom<HH, WW, C> G;
   const int e = blockIdx.x * PC_WG + threadIdx.x;
   const size_t mem = pc_member<MEMBERS>();
+  if constexpr (HYPER) a.lr = (float)a.member_hyper[mem].lr;
   const float *ws = pc_ws<MEMBERS>(a);
   const long long step = *reinterpret_cast<const long long *>(ws);  // (the forward launch's copy: the step counter is written below)
   if (e < G::P) {
@@ -494,28 +506,30 @@ bool ppo_cnn_shape_supported(int height, int width, int n_channels) {
   return shape && (n_channels == 4 || n_channels == 5 || n_channels == 8);
 }
 
-template <int HH, int WW, int C, bool MEMBERS>
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
 static hipError_t launch_ppo_cnn_shape(const PpoCnnArgs &a, int n_epochs, int n_members, hipStream_t st) {
   typedef PcGeom<HH, WW, C> G;
   static_assert(G::P == pc_params(HH, WW, C), "parameter map");
   const unsigned ny = MEMBERS ? (unsigned)n_members : 1u;
   for (int epoch = 0; epoch < n_epochs; ++epoch) {
     ppo_cnn_forward_kernel<HH, WW, C, MEMBERS><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_backward_kernel<HH, WW, C, MEMBERS><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_adam_kernel<HH, WW, C, MEMBERS><<<dim3((G::P + PC_WG - 1) / PC_WG, ny), dim3(PC_WG), 0, st>>>(a);
+    ppo_cnn_backward_kernel<HH, WW, C, MEMBERS, HYPER><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
+    ppo_cnn_adam_kernel<HH, WW, C, MEMBERS, HYPER><<<dim3((G::P + PC_WG - 1) / PC_WG, ny), dim3(PC_WG), 0, st>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys) {
+hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys,
+                                 const PpoMemberHyper *member_hyper) {
   (void)hipGetLastError();
   const int H = sh.rules_host.height, W = sh.rules_host.width, C = P.n_channels;
   if (!ppo_cnn_shape_supported(H, W, C) || P.batch < 2 || P.batch > 64 || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 ||
       P.n_trajectories >= (1ll << 31) || !P.workspace)
     return hipErrorInvalidValue;
   if (n_members < 0 || n_members > 65535 || (n_members > 0 && P.n_trajectories % n_members != 0)) return hipErrorInvalidValue;  // (gridDim.y)
+  if (member_hyper && n_members < 1) return hipErrorInvalidValue;
   PpoCnnArgs a;
   a.states = P.states; a.actions = P.actions; a.returns = P.returns; a.lengths = P.lengths;
   a.T = P.horizon; a.N = P.n_trajectories;
@@ -530,8 +544,14 @@ hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStr
   a.member_keys = member_keys;
   a.ws_stride = ppo_cnn_members_stride_bytes(H, W, C, P.batch) / sizeof(float);
   a.n_epochs = P.n_epochs;
+  a.member_hyper = member_hyper;
 #define SGK_PC_LAUNCH_C(HV, WV)                                                                                            \
   do {                                                                                                                     \
+    if (member_hyper) {                                                                                                    \
+      if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, true, true>(a, P.n_epochs, n_members, st);                        \
+      if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, true, true>(a, P.n_epochs, n_members, st);                        \
+      return launch_ppo_cnn_shape<HV, WV, 8, true, true>(a, P.n_epochs, n_members, st);                                    \
+    }                                                                                                                      \
     if (n_members > 0) {                                                                                                   \
       if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, true>(a, P.n_epochs, n_members, st);                              \
       if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, true>(a, P.n_epochs, n_members, st);                              \

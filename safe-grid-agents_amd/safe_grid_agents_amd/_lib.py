@@ -89,6 +89,20 @@ class SgkPpoCnnLearner(ctypes.Structure):
                 + [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "clipping", "critic_coeff", "entropy_bonus")])
 
 
+class SgkPpoMemberHyper(ctypes.Structure):
+    """sgk_ppo_member_hyper: one member's values, as a float64 [4] row of a device tensor holds them."""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "clipping", "critic_coeff", "entropy_bonus")]
+
+
+class SgkDqnMemberHyper(ctypes.Structure):
+    """sgk_dqn_member_hyper: one member's values, as a float64 [2] row of a device tensor holds them."""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "discount")]
+
+
+PPO_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkPpoMemberHyper._fields_)
+DQN_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkDqnMemberHyper._fields_)
+
+
 def build(force=False, verbose=False):
     """Compile libsgk.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))]
@@ -151,6 +165,7 @@ _SIGNATURES = {
     "sgk_dqn_sgd_step_reset_store": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner), ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
     "sgk_dqn_members_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
     "sgk_dqn_sgd_step_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner), ctypes.c_int32, _V, _V]),
+    "sgk_dqn_sgd_step_members_hyper": (ctypes.c_int, [_V, ctypes.POINTER(SgkDqnLearner), ctypes.c_int32, _V, _V, _V]),
     "sgk_convq_act": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_double, ctypes.c_uint64, _V, _V, _V, _V]),
     "sgk_convq_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_uint64, _V, _V, _V]),
     "sgk_convq_rollout": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.c_double, ctypes.c_uint64, ctypes.c_int32,
@@ -161,10 +176,12 @@ _SIGNATURES = {
     "sgk_reset_done_store": (ctypes.c_int, [_V, ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
     "sgk_ppo_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner)]),
     "sgk_ppo_epochs_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner), ctypes.c_int32, _V]),
+    "sgk_ppo_epochs_members_hyper": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner), ctypes.c_int32, _V, _V]),
     "sgk_ppo_cnn_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner)]),
     "sgk_ppo_cnn_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
     "sgk_ppo_cnn_epochs_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), ctypes.c_int32, _V]),
     "sgk_ppo_cnn_members_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "sgk_ppo_cnn_epochs_members_hyper": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), ctypes.c_int32, _V, _V]),
     "sgk_replay_store": (ctypes.c_int, [_V, ctypes.c_int32, _V, ctypes.c_int32, ctypes.c_int64, _V, _V, _V, _V, _V, _V]),
     "sgk_categorical_sample": (ctypes.c_int, [_V, _V, ctypes.c_uint64, _V, _V]),
     "sgk_policy_sample": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_uint64, _V, _V, _V]),
@@ -172,7 +189,11 @@ _SIGNATURES = {
                                           ctypes.c_int32, ctypes.c_uint32, _V, _V, _V]),
     "sgk_policy_rollout_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                                   ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V]),
+    "sgk_policy_rollout_members_eps": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                                      ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V, _V]),
     "sgk_discounted_returns": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_double]),
+    "sgk_discount_powers": (ctypes.c_int, [ctypes.c_double, ctypes.c_int32, _V]),
+    "sgk_discounted_returns_members": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _V]),
     "sgk_copy_boards": (ctypes.c_int, [_V, _V]),
     "sgk_copy_step_records": (ctypes.c_int, [_V, _V]),
     "sgk_copy_episode_state": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V]),
@@ -267,6 +288,16 @@ def issue_peak(device=0, waves_per_simd=8):
     v, s = ctypes.c_double(0.0), ctypes.c_double(0.0)
     check(load().sgk_issue_peak(int(device), int(waves_per_simd), ctypes.byref(v), ctypes.byref(s)))
     return v.value, s.value
+
+
+def discount_powers(discount, t_max):
+    """sgk_discount_powers: numpy float32 [t_max], element t = float32(discount ** t) -- a row of sgk_discounted_returns_members' table
+    (host only: no device is touched)."""
+    import numpy as np
+
+    out = np.empty(int(t_max), dtype=np.float32)
+    check(load().sgk_discount_powers(float(discount), int(t_max), out.ctypes.data))
+    return out
 
 
 def device_count():

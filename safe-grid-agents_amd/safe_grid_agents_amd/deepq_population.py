@@ -5,12 +5,14 @@
                            member axis in one contiguous tensor [M, ...]; the replay ring is ONE DeviceReplay over all N envs, member m's
                            transitions its own columns. step() acts for every member in one launch (sgk_policy_rollout_members, one
                            step) and learns in two (sgk_dqn_sgd_step_members: the SGD kernel with one workgroup per member, then Adam
-                           over n_members x ceil(P / 256) workgroups). All members share every hyper-parameter and the epsilon schedule;
-                           they differ in their weights, their envs and their draws, as M runs of the reference with different seeds do.
+                           over n_members x ceil(P / 256) workgroups). The members differ in their weights, their envs and their
+                           draws, as M runs of the reference with different seeds do -- and, with member_hyper, in lr, discount and the
+                           starting epsilon (sgk_dqn_sgd_step_members_hyper, sgk_policy_rollout_members_eps): a sweep in the same
+                           launches, the values read from device memory. epsilon_anneal and the schedule's shape stay shared.
 
 What member m computes is what a BatchedDeepQAgent(sgd_steps=1, fused_learn=True) computes on a handle of E envs created at
-env_index_base + m * E with the handle's seed, member m's weights and member_keys[m] as the key of its minibatch draws -- bit for bit
-(tests/test_gpu_dqn_members.py), and through that the reference's own run (tests/golden/batched_dqn_*.npz).
+env_index_base + m * E with the handle's seed, member m's weights, member_keys[m] as the key of its minibatch draws and member m's
+lr, discount and epsilon in its `args` -- bit for bit (tests/test_gpu_dqn_members.py, tests/test_gpu_member_hyper.py), and through that the reference's own run (tests/golden/batched_dqn_*.npz).
 
 There is no torch path for a population: a shape without a kernel is a ValueError in the constructor.
 """
@@ -20,6 +22,7 @@ import torch
 
 from . import _lib
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
+from .member_hyper import DQN_NAMES, resolve, validate_values
 from .metering import BatchMetrics
 from .ppo_population import FUSED_CELLS, _as_i64, default_member_seed
 
@@ -56,13 +59,23 @@ class BatchedDeepQPopulation:
     member m's initial weights are what BatchedDeepQAgent.build_Q gives on the CPU under torch.manual_seed(member_seeds[m]), Q first,
     then the target, initialised independently as value.py:82-84 does (default: default_member_seed(args.seed, m)); member_keys: the
     Philox key of member m's minibatch draws (default: the seeds). The action draws are keyed by the env's seed and the GLOBAL env
-    index, as everywhere. sgd_steps learner calls per lockstep step; reference_loss_broadcast as for BatchedDeepQAgent."""
+    index, as everywhere. sgd_steps learner calls per lockstep step; reference_loss_broadcast as for BatchedDeepQAgent.
+
+    member_hyper: None (every member runs with args' values, the shared-hyper entry points), or {name: M floats} for names of lr,
+    discount, epsilon (the schedule's starting value); the others keep args' value for every member. `member_values` then holds
+    {name: [M floats]} on the host and `hyper` the device tensors the kernels read:
+      hyper["learner"]   float64 [M, 2], rows of sgk_dqn_member_hyper (lr, discount)
+      hyper["epsilon0"]  float64 [M], the starting values;  hyper["epsilon"]  float64 [M], the annealed values of the current step
+    The annealed values are computed ON THE DEVICE, once per step(): three elementwise float64 kernels evaluate update_epsilon's
+    expression 1.0 - (1 - eps0) * t / anneal for every member in its own order of operations (IEEE double: the host's bits), so
+    step() makes no host synchronisation and no host-to-device copy. set_member_hyper copies into these tensors: the kernels and
+    any recorded graph keep their addresses."""
 
     torch = torch  # (the two BatchedDeepQAgent methods borrowed below read self.torch)
     build_Q = BatchedDeepQAgent.build_Q
 
     def __init__(self, env, args, n_members, member_seeds=None, member_keys=None, replay_slices=8, sgd_steps=1,
-                 reference_loss_broadcast=True):
+                 reference_loss_broadcast=True, member_hyper=None):
         M = int(n_members)
         hidden, layers, batch = int(getattr(args, "n_hidden", 0) or 0), int(args.n_layers), int(args.batch_size)
         if M < 1 or env.n_envs % M:
@@ -75,6 +88,9 @@ class BatchedDeepQPopulation:
             raise ValueError("a Deep-Q population needs 1 <= batch_size <= 64 (sgk_dqn_sgd_step_members), not %d" % batch)
         if env.n_cells not in FUSED_CELLS or env.action_space.n != 4:
             raise ValueError("the fused policy kernel does not cover %s (%d cells, %d actions)" % (env.name, env.n_cells, env.action_space.n))
+        self.member_values = self.hyper = None
+        if member_hyper is not None:  # (validation only, before anything touches the device)
+            self.member_values = resolve(member_hyper, DQN_NAMES, {k: float(getattr(args, k)) for k in DQN_NAMES}, M)
         self.env, self.n_members, self.member_envs = env, M, env.n_envs // M
         self.device = "cuda:%d" % env.device
         self.n_hidden, self.batch_size, self.sgd_steps = hidden, batch, int(sgd_steps)
@@ -91,6 +107,13 @@ class BatchedDeepQPopulation:
             raise ValueError("member_seeds / member_keys need one entry per member (%d)" % M)
         self.member_keys = torch.tensor(_as_i64(keys), dtype=torch.int64, device=self.device)
         K0, H, dev = env.n_cells, hidden, self.device
+        if self.member_values is not None:
+            v, f64 = self.member_values, dict(dtype=torch.float64, device=dev)
+            self.hyper = {"learner": torch.tensor([[v["lr"][m], v["discount"][m]] for m in range(M)], **f64),
+                          "epsilon0": torch.tensor(v["epsilon"], **f64), "epsilon": torch.empty(M, **f64)}
+            self._one_minus_eps0 = torch.tensor([1 - e for e in v["epsilon"]], **f64)  # (the host's own 1 - eps0)
+            self._zero_eps = torch.zeros(M, **f64)
+            self._eps_t = None  # the step hyper["epsilon"] holds the values of
         self.q_body, self.action_n = "mlp", env.action_space.n  # (what build_Q reads)
         q_dicts, t_dicts = [], []
         for s in self.member_seeds:  # (on the CPU: torch.nn.Linear draws its initial weights from the CPU generator)
@@ -158,14 +181,50 @@ class BatchedDeepQPopulation:
             raise IndexError("member %d of %d" % (m, self.n_members))
         return m
 
-    def member_state(self, m):
-        """{"Q": state_dict, "target_Q": state_dict} of member m under BatchedDeepQAgent's key names (copies)."""
-        m = self._member_index(m)
-        return {"Q": unstack_state_dict(self.cur, m), "target_Q": unstack_state_dict(self.target, m)}
+    def set_member_hyper(self, name, values):
+        """Member m's `name` <- values[m] (validated: ValueError), copied INTO the device tensors (no new allocation): the next step()
+        / learn_batch() -- a replay of a recorded one included -- runs with the new values. "epsilon" is the schedule's starting
+        value. A population built without member_hyper has no per-member tensors: ValueError."""
+        if self.hyper is None:
+            raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+        if name not in DQN_NAMES:
+            raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(DQN_NAMES)))
+        vals = validate_values(name, values, self.n_members)
+        self.member_values[name] = vals
+        if name == "epsilon":
+            self.hyper["epsilon0"].copy_(torch.tensor(vals, dtype=torch.float64))
+            self._one_minus_eps0.copy_(torch.tensor([1 - e for e in vals], dtype=torch.float64))
+            self._eps_t = None
+        else:
+            self.hyper["learner"][:, DQN_NAMES.index(name)].copy_(torch.tensor(vals, dtype=torch.float64))
 
-    def load_member(self, m, q_state, target_state=None):
-        """Member m's Q-network <- a BatchedDeepQAgent.Q state dict; its target network <- target_state, or left alone."""
+    def member_hyper_of(self, m):
+        """{name: member m's value} for lr, discount, epsilon (the shared values without member_hyper): what the `args` of the single
+        agent that member m equals carry."""
         m = self._member_index(m)
+        if self.member_values is None:
+            return {"lr": self.lr, "discount": self.discount, "epsilon": self.eps0}
+        return {k: self.member_values[k][m] for k in DQN_NAMES}
+
+    def member_state(self, m):
+        """{"Q": state_dict, "target_Q": state_dict, "hyper": {lr, discount, epsilon}} of member m: the networks under
+        BatchedDeepQAgent's key names (copies) and the hyper-parameters of the single agent member m equals."""
+        m = self._member_index(m)
+        return {"Q": unstack_state_dict(self.cur, m), "target_Q": unstack_state_dict(self.target, m), "hyper": self.member_hyper_of(m)}
+
+    def load_member(self, m, q_state, target_state=None, hyper=None):
+        """Member m's Q-network <- a BatchedDeepQAgent.Q state dict; its target network <- target_state, or left alone; its
+        hyper-parameters <- hyper ({name: value}; a population with member_hyper only), or left alone."""
+        m = self._member_index(m)
+        if hyper is not None:
+            if self.hyper is None:
+                raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+            for name, value in dict(hyper).items():
+                if name not in DQN_NAMES:
+                    raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(DQN_NAMES)))
+                vals = list(self.member_values[name])
+                vals[m] = value
+                self.set_member_hyper(name, vals)
         for dst, state in ((self.cur, q_state), (self.target, target_state)):
             if state is None:
                 continue
@@ -179,11 +238,22 @@ class BatchedDeepQPopulation:
         for k, t in self.target_t.items():
             t[m].copy_(self.target[k[:-1]][m].t())
 
-    # epsilon schedule of DeepQAgent (value.py:70-76,142-146), shared: the members are in lockstep and it depends on t alone
+    # epsilon schedule of DeepQAgent (value.py:70-76,142-146): the members are in lockstep and its shape depends on t alone; shared,
+    # or -- with member_hyper -- one starting value per member
     @property
     def epsilon(self):
+        """The current epsilon: a float, or with member_hyper the float64 [M] device tensor hyper["epsilon"] (see the class
+        docstring: computed on the device, no synchronisation)."""
         t = min(self.t, self.anneal - 1)
-        return 1.0 - (1 - self.eps0) * t / self.anneal
+        if self.hyper is None:
+            return 1.0 - (1 - self.eps0) * t / self.anneal
+        eps = self.hyper["epsilon"]
+        if self._eps_t != t:  # 1.0 - ((1 - eps0) * t) / anneal, update_epsilon's order of operations, in float64
+            torch.mul(self._one_minus_eps0, float(t), out=eps)
+            eps.div_(float(self.anneal))
+            eps.neg_().add_(1.0)  # (1.0 - x == -x + 1.0 in IEEE arithmetic)
+            self._eps_t = t
+        return eps
 
     def update_epsilon(self):
         self.t += 1
@@ -279,7 +349,8 @@ class BatchedDeepQPopulation:
         L.slices_filled = int(self.replay.filled)
         L.rows = None if rows is None else self.env._check(rows, "rows", shape=shape, dtypes=("int64",)).data_ptr()
         L.rows_out = None if rows_out is None else self.env._check(rows_out, "rows_out", shape=shape, dtypes=("int64",)).data_ptr()
-        self.env.dqn_sgd_step_members(L, self.n_members, self.member_keys, self.workspace)
+        self.env.dqn_sgd_step_members(L, self.n_members, self.member_keys, self.workspace,
+                                      member_hyper=None if self.hyper is None else self.hyper["learner"])
         self.last_loss = self.loss
         return self.loss
 
@@ -290,9 +361,13 @@ class BatchedDeepQPopulation:
         if learn and not rp.states_ready(env):
             rp.store(env, 0)  # the boards the agents act on are the transitions' states (already there when the previous step left them)
         # one step of the members rollout = sgk_policy_act + sgk_step for every member's envs, each with its own Q-network
-        env.policy_rollout_members(self.greedy_weights(), self.n_members, 1, mode="greedy", epsilon=self.epsilon if explore else 0.0,
+        if self.hyper is None:
+            eps, member_eps = (self.epsilon if explore else 0.0), None
+        else:
+            eps, member_eps = 0.0, (self.epsilon if explore else self._zero_eps)
+        env.policy_rollout_members(self.greedy_weights(), self.n_members, 1, mode="greedy", epsilon=eps,
                                    draw_index0=self.t, auto_reset=not learn, actions=self._actions,
-                                   member_metrics=self.member_metrics)
+                                   member_metrics=self.member_metrics, member_epsilon=member_eps)
         actions = self._actions[0]
         if learn:
             rp.store(env, 1, actions=actions, cheat=cheat)  # the rest of the add: successor boards, action, reward, terminal

@@ -814,11 +814,12 @@ class BatchedGridworldEnv:
         return _lib.SgkMlpWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1t", "b1", "w2", "b2", "w3t", "b3")), h)
 
     def policy_rollout_members(self, weights, n_members, n_steps, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False,
-                               states=None, actions=None, recs=None, mask_finished=False, member_metrics=None):
+                               states=None, actions=None, recs=None, mask_finished=False, member_metrics=None, member_epsilon=None):
         """policy_rollout for n_members independent policies in ONE HIP launch (sgk_policy_rollout_members): member m acts in the envs
         m * E .. (m + 1) * E - 1 (E = N / n_members) with slice m of `weights`, tensors stacked on a leading member axis (see
         _member_weights_arg). Outputs as for policy_rollout; member_metrics: int64 [n_members, 16] on this device that each member's
-        episodes are also booked in (sums added, maxima raised), or None."""
+        episodes are also booked in (sums added, maxima raised), or None. member_epsilon: float64 [n_members] on this device, member
+        m's epsilon in mode "greedy" instead of `epsilon` (sgk_policy_rollout_members_eps; the kernel reads it when it runs), or None."""
         n_members = int(n_members)
         if n_members < 1 or self.n_envs % n_members:
             raise ValueError("n_envs (%d) is not a multiple of n_members (%d)" % (self.n_envs, n_members))
@@ -834,21 +835,34 @@ class BatchedGridworldEnv:
         n = self.n_envs
         args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
                 ptr(recs, (n_steps, n, 4), "recs", "int8"), ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"))
+        fn = self.lib.sgk_policy_rollout_members
+        if member_epsilon is not None:
+            fn, args = self.lib.sgk_policy_rollout_members_eps, args + (ptr(member_epsilon, (n_members,), "member_epsilon", "float64"),)
         self._version += 1
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_policy_rollout_members(
+        _lib.check(fn(
             self._h.ptr, ctypes.byref(w), n_members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
             (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
         self._sync_lib_to_torch()
 
-    def ppo_epochs_members(self, learner, n_members, member_keys=None):
+    def _member_hyper_arg(self, member_hyper, n_members, n_fields):
+        """The device pointer of a float64 [n_members, n_fields] tensor: rows of sgk_ppo_member_hyper (4) / sgk_dqn_member_hyper (2)."""
+        return ctypes.c_void_p(self._check(member_hyper, "member_hyper", shape=(int(n_members), n_fields), dtypes=("float64",)).data_ptr())
+
+    def ppo_epochs_members(self, learner, n_members, member_keys=None, member_hyper=None):
         """One PPO learn() call of n_members independent PPOMLPAgents in ONE HIP launch (sgk_ppo_epochs_members); `learner` is a filled
-        _lib.SgkPpoLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None."""
+        _lib.SgkPpoLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None.
+        member_hyper: float64 [n_members, 4] on this device, rows (lr, clipping, critic_coeff, entropy_bonus) that replace the learner's
+        four (sgk_ppo_epochs_members_hyper), or None."""
         kp = None
         if member_keys is not None:
             kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
+        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 4)
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_ppo_epochs_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp))
+        if hp is None:
+            _lib.check(self.lib.sgk_ppo_epochs_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp))
+        else:
+            _lib.check(self.lib.sgk_ppo_epochs_members_hyper(self._h.ptr, ctypes.byref(learner), int(n_members), kp, hp))
         self._sync_lib_to_torch()
 
     def dqn_members_workspace_bytes(self, n_hidden, n_members):
@@ -859,10 +873,11 @@ class BatchedGridworldEnv:
             _lib.check(_lib.ERR_INVALID)
         return int(nbytes)
 
-    def dqn_sgd_step_members(self, learner, n_members, member_keys=None, workspace=None):
+    def dqn_sgd_step_members(self, learner, n_members, member_keys=None, workspace=None, member_hyper=None):
         """One DeepQAgent.learn() of n_members independent agents in two HIP launches (sgk_dqn_sgd_step_members); `learner` is a filled
         _lib.SgkDqnLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None,
-        workspace a uint8 device tensor of dqn_members_workspace_bytes() bytes that the caller keeps alive."""
+        workspace a uint8 device tensor of dqn_members_workspace_bytes() bytes that the caller keeps alive. member_hyper: float64
+        [n_members, 2] on this device, rows (lr, discount) that replace the learner's two (sgk_dqn_sgd_step_members_hyper), or None."""
         kp = wp = None
         if member_keys is not None:
             kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
@@ -872,8 +887,12 @@ class BatchedGridworldEnv:
             if need is None:
                 need = self._dqn_ws_bytes[key] = self.dqn_members_workspace_bytes(*key)
             wp = ctypes.c_void_p(self._check(workspace, "workspace", numel=need, dtypes=("uint8",)).data_ptr())
+        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 2)
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_dqn_sgd_step_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp))
+        if hp is None:
+            _lib.check(self.lib.sgk_dqn_sgd_step_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp))
+        else:
+            _lib.check(self.lib.sgk_dqn_sgd_step_members_hyper(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp, hp))
         self._sync_lib_to_torch()
 
     def ppo_cnn_epochs(self, learner):
@@ -939,18 +958,23 @@ class BatchedGridworldEnv:
             _lib.check(_lib.ERR_INVALID)
         return int(nbytes)
 
-    def ppo_cnn_epochs_members(self, learner, n_members, member_keys=None):
+    def ppo_cnn_epochs_members(self, learner, n_members, member_keys=None, member_hyper=None):
         """One learn() call of n_members independent PPOCNNAgents, three HIP launches per epoch (sgk_ppo_cnn_epochs_members); `learner`
         is a filled _lib.SgkPpoCnnLearner addressing member 0 of the stacked tensors, whose workspace holds
-        ppo_cnn_members_workspace_bytes() bytes; member_keys a uint64-as-int64 [n_members] device tensor or None."""
+        ppo_cnn_members_workspace_bytes() bytes; member_keys a uint64-as-int64 [n_members] device tensor or None. member_hyper: as
+        for ppo_epochs_members (sgk_ppo_cnn_epochs_members_hyper), or None."""
         n_members = int(n_members)
         if n_members < 1 or int(learner.n_trajectories) % n_members:
             raise ValueError("n_trajectories (%d) is not a multiple of n_members (%d)" % (int(learner.n_trajectories), n_members))
         kp = None
         if member_keys is not None:
             kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(n_members,), dtypes=("int64",)).data_ptr())
+        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 4)
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_ppo_cnn_epochs_members(self._h.ptr, ctypes.byref(learner), n_members, kp))
+        if hp is None:
+            _lib.check(self.lib.sgk_ppo_cnn_epochs_members(self._h.ptr, ctypes.byref(learner), n_members, kp))
+        else:
+            _lib.check(self.lib.sgk_ppo_cnn_epochs_members_hyper(self._h.ptr, ctypes.byref(learner), n_members, kp, hp))
         self._sync_lib_to_torch()
 
     def discounted_returns(self, rewards, discount, lengths=None, out=None):
@@ -973,6 +997,34 @@ class BatchedGridworldEnv:
         _lib.check(self.lib.sgk_discounted_returns(self._h.ptr, ctypes.c_void_p(rewards.data_ptr()), lp,
                                                    ctypes.c_void_p(out.data_ptr()), rewards.shape[0], rewards.shape[1],
                                                    float(discount)))
+        self._sync_lib_to_torch()
+        return out
+
+    def discounted_returns_members(self, rewards, gamma_pow, lengths=None, out=None):
+        """discounted_returns with one discount per member (sgk_discounted_returns_members): gamma_pow float32 [n_members, T] on this
+        GPU, row m = _lib.discount_powers(member m's discount, T); trajectory i of rewards float32 [n_trajectories, T] reads row
+        i // (n_trajectories // n_members). No allocation beyond `out`, no host synchronisation: the call can be recorded in a graph
+        (lengths then int32 and contiguous already)."""
+        import torch
+
+        rewards = self._check(rewards.contiguous() if isinstance(rewards, torch.Tensor) else rewards, "rewards", dtypes=("float32",))
+        if rewards.dim() != 2:
+            raise ValueError("rewards must be [n_trajectories, T]")
+        n, T = int(rewards.shape[0]), int(rewards.shape[1])
+        self._check(gamma_pow, "gamma_pow", dtypes=("float32",))
+        if gamma_pow.dim() != 2 or int(gamma_pow.shape[1]) != T or int(gamma_pow.shape[0]) < 1 or n % int(gamma_pow.shape[0]):
+            raise ValueError("gamma_pow must be [n_members, %d] with n_trajectories (%d) a multiple of n_members" % (T, n))
+        if out is None:
+            out = torch.zeros_like(rewards)
+        self._check(out, "out", shape=tuple(rewards.shape), dtypes=("float32",))
+        lp = None
+        if lengths is not None:
+            lengths = self._check(lengths, "lengths", numel=n, contiguous=False).to(torch.int32).contiguous()
+            lp = ctypes.c_void_p(lengths.data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_discounted_returns_members(self._h.ptr, ctypes.c_void_p(rewards.data_ptr()), lp,
+                                                           ctypes.c_void_p(out.data_ptr()), n, T, int(gamma_pow.shape[0]),
+                                                           ctypes.c_void_p(gamma_pow.data_ptr())))
         self._sync_lib_to_torch()
         return out
 

@@ -268,9 +268,11 @@ def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buf
     return rollout_from_records(env, buf, discount, cheat=cheat, masked=fused is not None)
 
 
-def rollout_from_records(env, buf, discount, cheat=False, masked=False):
+def rollout_from_records(env, buf, discount, cheat=False, masked=False, gamma_pow=None):
     """The second half of batched_gather_rollout: lengths, rewards and the discounted returns from the T step records in `buf`
-    (rollout_buffers), the env reset. masked: the kernel that wrote states / actions already stored zeros past an episode's end."""
+    (rollout_buffers), the env reset. masked: the kernel that wrote states / actions already stored zeros past an episode's end.
+    gamma_pow: a population's per-member table, float32 [M, T] on the device (row m = float32(discount_m ** t)): trajectory i is
+    discounted with row i // (N // M) and `discount` is not read (sgk_discounted_returns_members); None: `discount` for all."""
     import torch
 
     states, actions, recs = buf["states"], buf["actions"], buf["recs"]
@@ -293,7 +295,10 @@ def rollout_from_records(env, buf, discount, cheat=False, masked=False):
         if not masked:
             states.mul_(live.unsqueeze(2))
     returns.zero_()
-    env.discounted_returns(rewards, discount, lengths=lengths, out=returns)
+    if gamma_pow is None:
+        env.discounted_returns(rewards, discount, lengths=lengths, out=returns)
+    else:
+        env.discounted_returns_members(rewards, gamma_pow, lengths=lengths, out=returns)
     env.reset()
     return BatchedRollout(states, actions, rewards, returns, lengths)
 

@@ -4,13 +4,14 @@
                             Each of the 14 parameters, Adam's moments and the old policy's ten tensors exists once per member, stacked
                             on a leading member axis in one contiguous tensor [M, ...]. gather_rollout() is ONE launch
                             (sgk_convq_rollout_members: a workgroup serves one member) + the returns scan, learn() is ONE call
-                            (sgk_ppo_cnn_epochs_members: three launches per epoch, a member axis on the grid). All members share every
-                            hyper-parameter; they differ in their weights, their envs and their draws, as M runs of the reference with
-                            different seeds do.
+                            (sgk_ppo_cnn_epochs_members: three launches per epoch, a member axis on the grid). The members differ in
+                            their weights, their envs and their draws, as M runs of the reference with different seeds do -- and, with
+                            member_hyper, in lr, clipping, critic_coeff, entropy_bonus and discount (sgk_ppo_cnn_epochs_members_hyper,
+                            sgk_discounted_returns_members): a sweep in the same launches, the values read from device memory.
 
 What member m computes is what a BatchedPPOAgent(body="cnn", fused_conv_learn=True) computes on a handle of E envs created at
-env_index_base + m * E with the handle's seed, member m's weights and member_keys[m] as the key of its minibatch draws -- bit for bit
-(tests/test_gpu_ppo_cnn_members.py), and through that the reference's own run (tests/golden/batched_ppo_cnn_*.npz).
+env_index_base + m * E with the handle's seed, member m's weights, member_keys[m] as the key of its minibatch draws and member m's
+hyper-parameters in its `args` -- bit for bit (tests/test_gpu_ppo_cnn_members.py, tests/test_gpu_member_hyper.py), and through that the reference's own run (tests/golden/batched_ppo_cnn_*.npz).
 
 There is no torch path for a population: a shape without a kernel is a ValueError in the constructor.
 """
@@ -22,7 +23,7 @@ import torch
 from . import _lib
 from .metering import BatchMetrics
 from .ppo import BatchedPPOAgent, PPOCNNAgent
-from .ppo_population import _INT64_MIN, _MASK, _as_i64, default_member_seed
+from .ppo_population import _INT64_MIN, _MASK, PPOMemberHyper, _as_i64, default_member_seed
 
 # PPOCNNAgent's own parameters (state_dict keys, registration order) and the short names of the stacked tensors; the old policy reads
 # the first ten (trunk, bottleneck, actor path)
@@ -52,15 +53,16 @@ def unstack_state_dict(stacked, m):
     return {key: stacked[name][m].detach().clone() for key, name in zip(MEMBER_KEYS, PARAMS)}
 
 
-class BatchedPPOCNNPopulation:
+class BatchedPPOCNNPopulation(PPOMemberHyper):
     """M independent PPOCNNAgents over env's N = M x E envs (see the module docstring).
 
     args: the ppo-cnn flags (lr, discount, batch_size, epochs, clipping, entropy_bonus, critic_coeff, n_layers, n_channels, seed).
     member_seeds: member m's initial weights are those of PPOCNNAgent(env, args) built under torch.manual_seed(member_seeds[m])
     (default: default_member_seed(args.seed, m)); member_keys: the Philox key of member m's minibatch draws (default: the seeds).
-    The action draws are keyed by the env's seed and the GLOBAL env index, as everywhere."""
+    The action draws are keyed by the env's seed and the GLOBAL env index, as everywhere. member_hyper: as for BatchedPPOPopulation
+    (PPOMemberHyper)."""
 
-    def __init__(self, env, args, n_members, member_seeds=None, member_keys=None):
+    def __init__(self, env, args, n_members, member_seeds=None, member_keys=None, member_hyper=None):
         M = int(n_members)
         channels, layers, batch = int(getattr(args, "n_channels", 0) or 0), int(args.n_layers), int(args.batch_size)
         board = tuple(int(v) for v in env.observation_space.shape[-2:])
@@ -74,6 +76,7 @@ class BatchedPPOCNNPopulation:
             raise ValueError("a PPO-CNN population needs 2 <= batch_size <= 64 (sgk_ppo_cnn_epochs_members), not %d" % batch)
         if board not in FUSED_BOARDS or env.action_space.n != 4:
             raise ValueError("the fused conv kernels do not cover %s (a %dx%d board, %d actions)" % ((env.name,) + board + (env.action_space.n,)))
+        self._resolve_member_hyper(args, member_hyper, M)
         self.env, self.n_members, self.member_envs = env, M, env.n_envs // M
         self.device = "cuda:%d" % env.device
         self.n_channels, self.batch_size, self.epochs = channels, batch, int(args.epochs)
@@ -87,6 +90,7 @@ class BatchedPPOCNNPopulation:
         if len(self.member_seeds) != M or len(keys) != M:
             raise ValueError("member_seeds / member_keys need one entry per member (%d)" % M)
         self.member_keys = torch.tensor(_as_i64(keys), dtype=torch.int64, device=self.device)
+        self._alloc_member_hyper()
         self._cfg = types.SimpleNamespace(**vars(args))
         self._cfg.device = "cpu"
         dicts = []
@@ -126,10 +130,12 @@ class BatchedPPOCNNPopulation:
         out["step"] = self.step
         return out
 
-    def load_member(self, m, state_dict):
+    def load_member(self, m, state_dict, hyper=None):
         """Member m's current weights <- a PPOCNNAgent state dict (its own parameters; `old_policy.*` keys, when present, give the old
-        policy, else the old policy is left alone until the next sync())."""
+        policy, else the old policy is left alone until the next sync()). hyper: {name: value}, member m's hyper-parameters (a
+        population with member_hyper only), or None: left alone."""
         m = self._member_index(m)
+        self._load_member_hyper(m, hyper)
         for key, name in zip(MEMBER_KEYS, PARAMS):
             src = torch.as_tensor(state_dict[key]).to(device=self.device, dtype=torch.float32)
             if tuple(src.shape) != tuple(self.cur[name][m].shape):
@@ -140,11 +146,10 @@ class BatchedPPOCNNPopulation:
                 self.old[name][m].copy_(torch.as_tensor(state_dict["old_policy." + key]).to(device=self.device, dtype=torch.float32))
 
     def member(self, m):
-        """A PPOCNNAgent on the env's device holding COPIES of member m's weights (current and old policy)."""
+        """A PPOCNNAgent on the env's device holding COPIES of member m's weights (current and old policy), built from args that
+        carry member m's hyper-parameters."""
         m = self._member_index(m)
-        cfg = types.SimpleNamespace(**vars(self._cfg))
-        cfg.device = self.device
-        agent = PPOCNNAgent(self.env, cfg)
+        agent = PPOCNNAgent(self.env, self._member_cfg(m))
         sd = unstack_state_dict(self.cur, m)
         sd.update({"old_policy." + key: self.old[name][m].clone() for key, name in zip(MEMBER_KEYS[:N_OLD], PARAMS)})
         agent.load_state_dict(sd, strict=False)  # (the old policy's critic is never read)
@@ -193,7 +198,7 @@ class BatchedPPOCNNPopulation:
                                   auto_reset=False, states=buf["states"], actions=buf["actions"], recs=buf["recs"], mask_finished=True,
                                   member_metrics=self.member_metrics)
         self.draws += T
-        return rollout_from_records(env, buf, self.discount, cheat=cheat, masked=True)
+        return rollout_from_records(env, buf, self.discount, cheat=cheat, masked=True, gamma_pow=self._gamma_table(T))
 
     def evaluate(self, eval_timesteps):
         """batched_default_eval (reference eval.py:8-56) for every member's CURRENT policy, greedy: its two phases as two launches of
@@ -251,7 +256,7 @@ class BatchedPPOCNNPopulation:
             L.rows_out = ptr(chk(rows_out, "rows_out", shape=(M, self.epochs, self.batch_size), dtypes=("int64",)))
         L.lr, (L.beta1, L.beta2), L.eps = self.lr, self.betas, self.adam_eps
         L.clipping, L.critic_coeff, L.entropy_bonus = self.clipping, self.critic_coeff, self.entropy_bonus
-        env.ppo_cnn_epochs_members(L, M, self.member_keys)
+        env.ppo_cnn_epochs_members(L, M, self.member_keys, member_hyper=None if self.hyper is None else self.hyper["learner"])
         if history is not None:
             self._log_stats(history)
         return history

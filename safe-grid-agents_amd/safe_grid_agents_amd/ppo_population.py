@@ -3,13 +3,15 @@
   BatchedPPOPopulation   M PPOMLPAgents over one BatchedGridworldEnv of N = M x E envs; member m owns the envs m * E .. (m + 1) * E - 1.
                          Every parameter, Adam tensor and old-policy tensor exists once per member, stacked on a leading member axis in
                          one contiguous tensor [M, ...]. gather_rollout() is ONE launch (sgk_policy_rollout_members: a workgroup serves
-                         one member) + the returns scan, learn() is ONE launch (sgk_ppo_epochs_members: workgroup m = member m). All
-                         members share every hyper-parameter; they differ in their weights, their envs and their draws, as M runs of the
-                         reference with different seeds do.
+                         one member) + the returns scan, learn() is ONE launch (sgk_ppo_epochs_members: workgroup m = member m). The
+                         members differ in their weights, their envs and their draws, as M runs of the reference with different seeds
+                         do -- and, with member_hyper, in lr, clipping, critic_coeff, entropy_bonus and discount: a sweep in the same two
+                         launches (sgk_ppo_epochs_members_hyper, sgk_discounted_returns_members), the values read from device memory.
 
 What member m computes is what a BatchedPPOAgent computes on a handle of E envs created at env_index_base + m * E with the handle's
-seed, member m's weights and member_keys[m] as the key of its minibatch draws -- bit for bit (tests/test_gpu_ppo_members.py), and
-through that the reference's own run (tests/golden/batched_ppo_*.npz).
+seed, member m's weights, member_keys[m] as the key of its minibatch draws and member m's hyper-parameters in its `args` -- bit for
+bit (tests/test_gpu_ppo_members.py, tests/test_gpu_member_hyper.py), and through that the reference's own run
+(tests/golden/batched_ppo_*.npz).
 
 There is no torch path for a population: a shape without a kernel is a ValueError in the constructor.
 """
@@ -19,6 +21,7 @@ import types
 import torch
 
 from . import _lib
+from .member_hyper import PPO_NAMES, resolve, validate_values
 from .metering import BatchMetrics
 from .ppo import PPOMLPAgent
 
@@ -72,15 +75,103 @@ def _as_i64(values):
     return [v - 2 ** 64 if v >= 2 ** 63 else v for v in (int(x) & _MASK for x in values)]
 
 
-class BatchedPPOPopulation:
+class PPOMemberHyper:
+    """The per-member hyper-parameters of the two PPO populations (BatchedPPOPopulation, BatchedPPOCNNPopulation).
+
+    member_hyper=None: `hyper` is None and the population calls the shared-hyper entry points, exactly as without this class.
+    Else `member_values` holds {name: [M floats]} for all of PPO_NAMES on the host and `hyper` the device tensors the kernels read:
+      hyper["learner"]    float64 [M, 4], rows of sgk_ppo_member_hyper (lr, clipping, critic_coeff, entropy_bonus)
+      hyper["gamma_pow"]  float32 [M, T], row m = float32(discount_m ** t): the table of sgk_discounted_returns_members, made at the
+                          first gather_rollout for its horizon T (absent before)
+    set_member_hyper copies into them, so the kernels and any recorded graph keep their addresses and see the new values."""
+
+    hyper = None
+    member_values = None
+
+    def _resolve_member_hyper(self, args, member_hyper, n_members):
+        """Validation only (no device): ValueError for an unknown name, a wrong length, an invalid value."""
+        if member_hyper is not None:
+            defaults = {k: float(getattr(args, k)) for k in PPO_NAMES}
+            self.member_values = resolve(member_hyper, PPO_NAMES, defaults, n_members)
+
+    def _alloc_member_hyper(self):
+        if self.member_values is not None:
+            v, self._gamma = self.member_values, {}
+            rows = [[v[k][m] for k in PPO_NAMES[:4]] for m in range(self.n_members)]
+            self.hyper = {"learner": torch.tensor(rows, dtype=torch.float64, device=self.device)}
+
+    def set_member_hyper(self, name, values):
+        """Member m's `name` <- values[m] (validated: ValueError), copied INTO the device tensors (no new allocation): the next
+        learn() / gather_rollout() -- a replay of a recorded one included -- runs with the new values. A population built without
+        member_hyper has no per-member tensors: ValueError."""
+        if self.hyper is None:
+            raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+        if name not in PPO_NAMES:
+            raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(PPO_NAMES)))
+        vals = validate_values(name, values, self.n_members)
+        self.member_values[name] = vals
+        if name == "discount":
+            for T, table in self._gamma.items():
+                table.copy_(self._gamma_host(T))
+        else:
+            self.hyper["learner"][:, PPO_NAMES.index(name)].copy_(torch.tensor(vals, dtype=torch.float64))
+
+    def member_hyper_of(self, m):
+        """{name: member m's value} for all of PPO_NAMES (the shared values without member_hyper): what the `args` of the single agent
+        that member m equals carry."""
+        m = self._member_index(m)
+        if self.member_values is None:
+            return {"lr": self.lr, "clipping": self.clipping, "critic_coeff": self.critic_coeff, "entropy_bonus": self.entropy_bonus,
+                    "discount": self.discount}
+        return {k: self.member_values[k][m] for k in PPO_NAMES}
+
+    def _member_cfg(self, m):
+        """self._cfg with member m's hyper-parameters, on the env's device: the `args` of the single agent member m equals."""
+        cfg = types.SimpleNamespace(**vars(self._cfg))
+        cfg.device = self.device
+        vars(cfg).update(self.member_hyper_of(m))
+        return cfg
+
+    def _load_member_hyper(self, m, hyper):
+        """load_member's `hyper`: {name: value} for member m alone."""
+        if hyper is None:
+            return
+        if self.hyper is None:
+            raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+        for name, value in dict(hyper).items():
+            if name not in PPO_NAMES:
+                raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(PPO_NAMES)))
+            vals = list(self.member_values[name])
+            vals[m] = value
+            self.set_member_hyper(name, vals)
+
+    def _gamma_host(self, T):
+        import numpy as np
+
+        return torch.from_numpy(np.stack([_lib.discount_powers(d, T) for d in self.member_values["discount"]]))
+
+    def _gamma_table(self, T):
+        """hyper["gamma_pow"] for a horizon of T steps (None without member_hyper): made once per T, refreshed in place."""
+        if self.hyper is None:
+            return None
+        T = int(T)
+        if T not in self._gamma:
+            self._gamma[T] = self._gamma_host(T).to(self.device)
+        self.hyper["gamma_pow"] = self._gamma[T]
+        return self._gamma[T]
+
+
+class BatchedPPOPopulation(PPOMemberHyper):
     """M independent PPOMLPAgents over env's N = M x E envs (see the module docstring).
 
     args: the ppo-mlp flags (lr, discount, batch_size, epochs, clipping, entropy_bonus, critic_coeff, n_layers, n_hidden, seed).
     member_seeds: member m's initial weights are those of PPOMLPAgent(env, args) built under torch.manual_seed(member_seeds[m])
     (default: default_member_seed(args.seed, m)); member_keys: the Philox key of member m's minibatch draws (default: the seeds).
-    The action draws are keyed by the env's seed and the GLOBAL env index, as everywhere."""
+    The action draws are keyed by the env's seed and the GLOBAL env index, as everywhere. member_hyper: None (every member runs with
+    args' values, the shared-hyper entry points), or {name: M floats} for names of lr, clipping, critic_coeff, entropy_bonus, discount
+    (the others keep args' value for every member): see PPOMemberHyper."""
 
-    def __init__(self, env, args, n_members, member_seeds=None, member_keys=None):
+    def __init__(self, env, args, n_members, member_seeds=None, member_keys=None, member_hyper=None):
         M = int(n_members)
         hidden, layers, batch = int(getattr(args, "n_hidden", 0) or 0), int(args.n_layers), int(args.batch_size)
         if M < 1 or env.n_envs % M:
@@ -93,6 +184,7 @@ class BatchedPPOPopulation:
             raise ValueError("a PPO population needs 2 <= batch_size <= 64 (sgk_ppo_epochs_members), not %d" % batch)
         if env.n_cells not in FUSED_CELLS or env.action_space.n != 4:
             raise ValueError("the fused policy kernel does not cover %s (%d cells, %d actions)" % (env.name, env.n_cells, env.action_space.n))
+        self._resolve_member_hyper(args, member_hyper, M)
         self.env, self.n_members, self.member_envs = env, M, env.n_envs // M
         self.device = "cuda:%d" % env.device
         self.n_hidden, self.batch_size, self.epochs = hidden, batch, int(args.epochs)
@@ -106,6 +198,7 @@ class BatchedPPOPopulation:
         if len(self.member_seeds) != M or len(keys) != M:
             raise ValueError("member_seeds / member_keys need one entry per member (%d)" % M)
         self.member_keys = torch.tensor(_as_i64(keys), dtype=torch.int64, device=self.device)
+        self._alloc_member_hyper()
         self._cfg = types.SimpleNamespace(**vars(args))
         self._cfg.device = "cpu"
         dicts = []
@@ -160,10 +253,12 @@ class BatchedPPOPopulation:
         out["step"] = self.step
         return out
 
-    def load_member(self, m, state_dict):
+    def load_member(self, m, state_dict, hyper=None):
         """Member m's current weights <- a PPOMLPAgent state dict (its own parameters; `old_policy.*` keys, when present, give the old
-        policy, else the old policy is left alone until the next sync())."""
+        policy, else the old policy is left alone until the next sync()). hyper: {name: value}, member m's hyper-parameters (a
+        population with member_hyper only), or None: left alone."""
         m = self._member_index(m)
+        self._load_member_hyper(m, hyper)
         for key, name in zip(MEMBER_KEYS, PARAMS):
             src = torch.as_tensor(state_dict[key]).to(device=self.device, dtype=torch.float32)
             if tuple(src.shape) != tuple(self.cur[name][m].shape):
@@ -178,11 +273,10 @@ class BatchedPPOPopulation:
             old["b2"][m].copy_(o[3]); old["wa"][m].copy_(o[4]); old["w3t"][m].copy_(o[4].t()); old["ba"][m].copy_(o[5])
 
     def member(self, m):
-        """A PPOMLPAgent on the env's device holding COPIES of member m's weights (current and old policy)."""
+        """A PPOMLPAgent on the env's device holding COPIES of member m's weights (current and old policy), built from args that
+        carry member m's hyper-parameters."""
         m = self._member_index(m)
-        cfg = types.SimpleNamespace(**vars(self._cfg))
-        cfg.device = self.device
-        agent = PPOMLPAgent(self.env, cfg)
+        agent = PPOMLPAgent(self.env, self._member_cfg(m))
         own = unstack_state_dict(self.cur, m)
         old = self.old
         olds = {"network.0.0.weight": old["w1t"][m].t(), "network.0.0.bias": old["b1"][m], "network.1.0.0.weight": old["w2"][m],
@@ -238,7 +332,7 @@ class BatchedPPOPopulation:
                                    states=buf["states"], actions=buf["actions"], recs=buf["recs"], mask_finished=True,
                                    member_metrics=self.member_metrics)
         self.draws += T
-        return rollout_from_records(env, buf, self.discount, cheat=cheat, masked=True)
+        return rollout_from_records(env, buf, self.discount, cheat=cheat, masked=True, gamma_pow=self._gamma_table(T))
 
     def evaluate(self, eval_timesteps):
         """batched_default_eval (reference eval.py:8-56) for every member's CURRENT policy, greedy: its two phases as two launches of
@@ -300,7 +394,7 @@ class BatchedPPOPopulation:
             L.rows_out = ptr(chk(rows_out, "rows_out", shape=(M, self.epochs, self.batch_size), dtypes=("int64",)))
         L.lr, (L.beta1, L.beta2), L.eps = self.lr, self.betas, self.adam_eps
         L.clipping, L.critic_coeff, L.entropy_bonus = self.clipping, self.critic_coeff, self.entropy_bonus
-        env.ppo_epochs_members(L, M, self.member_keys)
+        env.ppo_epochs_members(L, M, self.member_keys, member_hyper=None if self.hyper is None else self.hyper["learner"])
         if history is not None:
             self._log_stats(history)
         return history

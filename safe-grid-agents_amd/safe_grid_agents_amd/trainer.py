@@ -13,6 +13,7 @@ import numpy as np
 from . import envs as _envs
 from .agents import AGENT_MAP
 from .loops import EVAL_MAP, LEARN_MAP, WARMUP_MAP
+from .member_hyper import parse_sweep, point_label, sweep_member_hyper, sweep_table
 from .metering import NullWriter, make_meters
 
 ENV_MAP = _envs.ENV_MAP
@@ -38,6 +39,11 @@ _CORE_FLAGS = [
     # in one batch of N = M x rollouts envs: M runs of the reference's experiment in lockstep on one GPU. An explicit -N must agree. With deep-q, M independent agents
     # (BatchedDeepQPopulation) of N / M envs each: the batch comes from -N, a multiple of M.
     ("members", "M", dict(type=int, default=0)),
+    # extension: with --members, `--sweep NAME=v1,v2,...` (repeatable) gives the members their own hyper-parameters: the grid is the
+    # Cartesian product of the lists in the order given (first flag slowest, G points), M a multiple of G, member m runs point m % G
+    # as replica m // G of it (member_hyper.parse_sweep). Names: lr, clipping, critic_coeff, entropy_bonus, discount (ppo-*); lr,
+    # discount, epsilon (deep-q).
+    ("sweep", "W", dict(action="append", default=None, metavar="NAME=v1,v2,...")),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -56,6 +62,8 @@ _PPO_FLAGS = [_LR,
               _LAYERS]
 # --members is also accepted behind the agent's own flags (`... deep-q -l 1e-3 --members 32`); absent there, the core flag's value stays
 _MEMBERS = ("members", "M", dict(type=int, default=argparse.SUPPRESS))
+# --sweep likewise (`... ppo-mlp -l 1e-3 -r 4 -e 2 --members 6 --sweep lr=1e-3,1e-2 --sweep clipping=0.1,0.2,0.5`)
+_SWEEP = ("sweep", "W", dict(action="append", default=argparse.SUPPRESS, metavar="NAME=v1,v2,..."))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -73,9 +81,9 @@ _AGENT_FLAGS = {
                ("q-body", "qb", dict(type=str, default="mlp", choices=("mlp", "cnn"),
                                      help="mlp: the reference's network (default, pinned); cnn: non-parity conv body, -N only")),
                ("n-channels", "ch", dict(type=int, default=5)),
-               _MEMBERS],
-    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS],
-    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS],
+               _MEMBERS, _SWEEP],
+    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP],
+    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP],
 }
 
 
@@ -184,6 +192,8 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     members = int(getattr(args, "members", 0) or 0)
     if members:
         members_n_envs(args)  # ppo-mlp, ppo-cnn: N = M x rollouts; deep-q: -N, a multiple of M
+    sweep = sweep_grid(args)  # --sweep: (names, grid) or None; SystemExit for a sweep that cannot run
+    member_hyper = sweep_member_hyper(sweep[0], sweep[1], members) if sweep else None
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -214,11 +224,12 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
         # the replay holds whole lockstep slices: as many as cover the reference's capacity per member, at least 2
         slices = max(2, -(-int(args.replay_capacity) // (env.n_envs // members)))
-        agent = BatchedDeepQPopulation(env, args, members, replay_slices=slices)
+        agent = BatchedDeepQPopulation(env, args, members, replay_slices=slices, member_hyper=member_hyper)
         agent.warmup(slices)  # dqn_warmup (warmup.py:8-23) of every member: random-action transitions fill the replay
         env.reset()
     elif members:
-        agent = (BatchedPPOCNNPopulation if args.agent_alias == "ppo-cnn" else BatchedPPOPopulation)(env, args, members)
+        agent = (BatchedPPOCNNPopulation if args.agent_alias == "ppo-cnn" else BatchedPPOPopulation)(env, args, members,
+                                                                                                     member_hyper=member_hyper)
     elif args.agent_alias in ("ppo-mlp", "ppo-cnn"):
         import torch
 
@@ -245,6 +256,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     deepq = args.agent_alias == "deep-q"
     history = {"writer": writer, "t": 0, "t_learn": 0}
     period = 0
+    per_member = None
     for episode in range(1, args.episodes + 1):
         if members and ppo:  # every member's rollout + epochs: two launches; the aggregate meters and the spread over the members
             per_member, bm = population_ppo_learn(agent, env, history, cheat=args.cheat)
@@ -273,8 +285,15 @@ def train_batched(args, writer_factory=None, reporter=_noop):
             per_member = agent.member_batch_metrics()
             for tag, name in (("Train/member_return", "returns"), ("Train/member_safety", "safeties")):
                 writer.add_histogram(tag, np.array([m.meter(name)["avg"] for m in per_member], dtype=np.float64), episode)
+        if sweep and per_member is not None:  # each grid point's return and safety, the mean over its replicas (members g, g + G, ...)
+            G = len(sweep[1])
+            for tag, name in (("Train/sweep_return", "returns"), ("Train/sweep_safety", "safeties")):
+                avgs = np.array([m.meter(name)["avg"] for m in per_member], dtype=np.float64)
+                for g, point in enumerate(sweep[1]):
+                    writer.add_scalar("%s/%s" % (tag, point_label(sweep[0], point)), float(avgs[g::G].mean()), episode)
         if agent is not None and not ppo:
-            writer.add_scalar("Train/epsilon", agent.epsilon, agent.t)
+            eps = agent.epsilon  # (a swept population: one value per member on the device; the scalar is their mean)
+            writer.add_scalar("Train/epsilon", float(eps.mean()) if hasattr(eps, "mean") else eps, agent.t)
         if deepq and agent.last_loss is not None:
             loss = agent.last_loss.mean() if members else agent.last_loss.reshape(-1)[0]  # (a population: the members' mean)
             writer.add_scalar("Train/value_loss", float(loss), agent.t)
@@ -290,7 +309,22 @@ def train_batched(args, writer_factory=None, reporter=_noop):
             period = _batched_eval(agent, env, args, writer, period, rank, sdist)
     if agent is not None:  # train.py:81: one more evaluation after the loop, unconditionally (also when the last episode had one)
         period = _batched_eval(agent, env, args, writer, period, rank, sdist)
+    if sweep and per_member is not None and rank == 0:  # the table, once: the last training period's episodes
+        print("#### SWEEP: %d grid points x %d replicas, return and safety of the last training period, mean +- std over replicas ####"
+              % (len(sweep[1]), members // len(sweep[1])))
+        for line in sweep_table(sweep[0], sweep[1], [m.meter("returns")["avg"] for m in per_member],
+                                [m.meter("safeties")["avg"] for m in per_member]):
+            print(line)
     return agent, env
+
+
+def sweep_grid(args):
+    """--sweep NAME=v1,v2,... flags of `args` -> (names, grid) (member_hyper.parse_sweep; SystemExit with the valid names for a sweep
+    that cannot run), or None without the flag."""
+    specs = getattr(args, "sweep", None)
+    if not specs:
+        return None
+    return parse_sweep(specs, args.agent_alias, int(getattr(args, "members", 0) or 0))
 
 
 def members_n_envs(args):
