@@ -789,6 +789,70 @@ SGK_API int sgk_discount_powers(double discount, int32_t t_max, float *out_host)
 SGK_API int sgk_discounted_returns_members(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
                                            int64_t n_trajectories, int32_t t_max, int32_t n_members, const float *gamma_pow_dev);
 
+/* ---- population-based training: "member d becomes member s" on the device ------------------------------------------------------
+ * The exploit / explore step over a population's stacked [n_members][...] tensors (the reference's multi-run story is Ray Tune
+ * random search, tune_config.py; this is the scheduler a Tune user reaches for next). Two kinds of launch on the handle's stream:
+ * sgk_members_select ranks the members and names every member's source, sgk_members_clone copies the sources' slabs. Both allocate
+ * nothing, never synchronise, are legal as the first call on a handle and inside a stream capture.
+ *
+ * The counter RNG's streams (ctr word 3 of Philox-4x32-10; the layout is part of the ABI): 0 random actions, 1 tabular-Q exploration,
+ * 2 epsilon-greedy, 3 categorical sampling, 4 the DQN minibatch, 5 the PPO minibatch, 6 the envs' own draws, 7 the explore step's
+ * factor choice (below). */
+#define SGK_MEMBERS_MAX 4096        /* n_members of sgk_members_select / sgk_members_clone: scores + order fill 48 KB of LDS */
+#define SGK_MEMBERS_MAX_TENSORS 64  /* descriptors per sgk_members_clone call: 1 KB of kernel arguments */
+#define SGK_MEMBERS_MAX_COLUMNS 8   /* columns of the hyper tensor sgk_members_select perturbs */
+#define SGK_MEMBERS_BAD_SOURCE 1    /* bit 0 of sgk_members_clone's status word */
+/* The explore step of sgk_members_select. hyper_dev: float64 [n_members][n_columns] in device memory, 1 <= n_columns <= 8 -- the rows
+ * of sgk_ppo_member_hyper (4 columns) or sgk_dqn_member_hyper (2). For every REPLACED member d with source s and every column k:
+ *   bit k of perturb_mask clear:  hyper[d][k] = hyper[s][k]
+ *   set:                          hyper[d][k] = min(max(hyper[s][k] * f, lo[k]), hi[k])   (one IEEE double multiply, round to nearest)
+ *   f = factor_up if x[0] & 1 else factor_down,  x = philox4x32_10(ctr = {d, k, (uint32_t)generation, 7}, key = {key_lo, key_hi})
+ * generation_dev: one int64 in device memory, read when the kernel runs and stored back + 1 after the rows are written, so a
+ * replayed graph draws fresh factors. Rows of members that are not replaced (the sources among them) are never written. Bits of
+ * perturb_mask at or above n_columns are ignored. */
+typedef struct sgk_members_explore {
+  double *hyper_dev;
+  int32_t n_columns;
+  uint32_t perturb_mask;
+  double factor_down, factor_up;
+  double lo[8], hi[8];
+  uint64_t key;
+  int64_t *generation_dev;
+} sgk_members_explore;
+/* Truncation selection in one launch of one workgroup. scores_dev: float64 [n_members] (higher is better; NaN is read as -inf);
+ * src_out_dev: int32 [n_members]. Member j ranks above member m iff s_j > s_m, or s_j == s_m and j < m (a total order: -0.0 == 0.0
+ * and equal scores fall back on the index); order[rank] = member. For i < n_replace: src[order[n_members - 1 - i]] = order[i] (the
+ * worst becomes the best, the second worst the second best, ...); every other member has src[m] = m. A source is therefore a fixed
+ * point (src[src[m]] == src[m]) and no source is a destination. explore: NULL, or the explore step above, run after the selection in
+ * the same launch. SGK_ERR_INVALID (nothing is launched or written) for a NULL pointer, n_members outside 1 .. 4096, n_replace
+ * outside 0 .. n_members / 2, n_columns outside 1 .. 8, a factor that is not finite or <= 0, lo[k] > hi[k] or a NaN bound (k <
+ * n_columns). The arguments are checked before the handle is looked at. */
+SGK_API int sgk_members_select(sgk_env *h, const double *scores_dev, int32_t n_members, int32_t n_replace, int32_t *src_out_dev,
+                               const sgk_members_explore *explore);
+/* One stacked tensor of sgk_members_clone: member m's slab is the bytes_per_member bytes at base + m * bytes_per_member. base is
+ * 4-byte aligned and bytes_per_member a multiple of 4 (a sliced view is fine). */
+typedef struct sgk_members_tensor {
+  void *base;
+  uint64_t bytes_per_member;
+} sgk_members_tensor;
+/* ONE launch that makes every replaced member's slab equal its source's, over n_tensors <= 64 stacked tensors: for every d with
+ * src_dev[d] != d and every tensor, the slab of src_dev[d] is copied over the slab of d. descs is a HOST array, passed to the kernel
+ * by value (no device table). The grid is (chunks, n_members): a workgroup whose member is not replaced returns at once, the others
+ * share the member's 4 KB tiles round-robin; a tensor whose base and bytes_per_member are 16-byte aligned moves 16 bytes per lane,
+ * any other 4. src_dev: int32 [n_members] in device memory, what sgk_members_select wrote. A src_dev[d] outside [0, n_members), or
+ * one that is not a fixed point (its source is itself a destination: the copy would race), copies NOTHING for d and sets
+ * SGK_MEMBERS_BAD_SOURCE in *status_dev (int32, device memory, the caller's; never cleared here; read it at the next
+ * synchronisation); the other members are served. SGK_ERR_INVALID (nothing is launched) for a NULL pointer, n_members outside 1 ..
+ * 4096, n_tensors outside 0 .. 64, a bytes_per_member that is no multiple of 4 and a base that is not 4-byte aligned. The arguments
+ * are checked before the handle is looked at. n_tensors = 0 launches nothing. */
+SGK_API int sgk_members_clone(sgk_env *h, const int32_t *src_dev, int32_t n_members, const sgk_members_tensor *descs, int32_t n_tensors,
+                              int32_t *status_dev);
+/* sgk_members_select's selection on the host, from host arrays (the same ranking code, compiled for the host): no handle, no device.
+ * SGK_ERR_INVALID as sgk_members_select. */
+SGK_API int sgk_members_select_host(const double *scores, int32_t n_members, int32_t n_replace, int32_t *src_out);
+/* The explore step's coin for (member, column) at `generation` under `key`: 1 (factor_up) or 0 (factor_down); no handle, no device. */
+SGK_API int sgk_members_explore_pick(uint64_t key, int64_t generation, int32_t member, int32_t column);
+
 /* What one unit of the integer rewards (step records, episode sums, the metrics vector's sums and maxima) is worth: 1.0, except
  * TomatoWatering's REWARD_FACTOR = 0.02 per watered tomato (the reference consumes the float: learn.py:38-48, meters.py:76-84).
  * Multiply in float64: count * scale is upstream's own expression. */

@@ -357,6 +357,14 @@ int sgk_create(int env_id, int64_t n_envs, int device, uint64_t seed, sgk_env **
     }                                                         \
   } while (0)
 
+// for the entry points that live beside their kernels (sgk_members.hip): the handle's checks, then its shard and current stream
+int sgk_handle_launch_site(sgk_env *h, const sgk::Shard **sh_out, hipStream_t *stream_out) try {
+  SGK_CHECK_HANDLE(h);
+  *sh_out = &h->sh;
+  *stream_out = h->stream;
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_reward_scale(sgk_env *h, double *scale_out) try {
   SGK_CHECK_HANDLE(h);
   if (!scale_out) return fail(SGK_ERR_INVALID, "scale_out is NULL");

@@ -236,6 +236,30 @@ size_t tabq_rollout_lds_bytes(const Shard &sh);
 hipError_t launch_tabq_eval(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st);
 hipError_t launch_tabq_eval_hbm(const Shard &sh, const TabqShard &tq, int64_t n_reset_steps, int64_t n_tail_steps, hipStream_t st);
 
+// population-based training (sgk_members.hip): the select + explore launch of one workgroup, the clone launch over (chunks, n_members)
+struct MembersExplore {
+  double *hyper;
+  int n_columns;
+  uint32_t mask;
+  double factor_down, factor_up;
+  double lo[8], hi[8];
+  uint64_t key;
+  long long *generation;
+};
+struct MembersTensor {
+  char *base;
+  uint64_t bytes;
+};
+struct MembersCloneArgs {
+  const int32_t *src;
+  int32_t *status;
+  int n_members, n_tensors;
+  MembersTensor t[SGK_MEMBERS_MAX_TENSORS];
+};
+hipError_t launch_members_select(const double *scores, int n_members, int n_replace, int32_t *src_out, const MembersExplore *explore,
+                                 hipStream_t st);
+hipError_t launch_members_clone(const Shard &sh, const MembersCloneArgs &a, hipStream_t st);
+
 int host_random_action(uint64_t seed, uint64_t env, uint64_t t);  // sgk_host_debug.cpp
 int host_debug_transition(const SgkRules &R, int agent_cell, int box_cell, int action, int out[5]);
 int host_debug_step(const SgkRules &R, uint64_t word, int n_resets, int action, uint64_t seed, uint64_t env, uint64_t *word_out,

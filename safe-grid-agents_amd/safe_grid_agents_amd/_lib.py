@@ -99,6 +99,19 @@ class SgkDqnMemberHyper(ctypes.Structure):
     _fields_ = [(k, ctypes.c_double) for k in ("lr", "discount")]
 
 
+class SgkMembersExplore(ctypes.Structure):
+    """sgk_members_explore: the explore step of sgk_members_select."""
+    _fields_ = [("hyper_dev", ctypes.c_void_p), ("n_columns", ctypes.c_int32), ("perturb_mask", ctypes.c_uint32),
+                ("factor_down", ctypes.c_double), ("factor_up", ctypes.c_double), ("lo", ctypes.c_double * 8), ("hi", ctypes.c_double * 8),
+                ("key", ctypes.c_uint64), ("generation_dev", ctypes.c_void_p)]
+
+
+class SgkMembersTensor(ctypes.Structure):
+    """sgk_members_tensor: one stacked tensor of sgk_members_clone."""
+    _fields_ = [("base", ctypes.c_void_p), ("bytes_per_member", ctypes.c_uint64)]
+
+
+MEMBERS_MAX, MEMBERS_MAX_TENSORS, MEMBERS_MAX_COLUMNS, MEMBERS_BAD_SOURCE = 4096, 64, 8, 1
 PPO_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkPpoMemberHyper._fields_)
 DQN_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkDqnMemberHyper._fields_)
 
@@ -194,6 +207,10 @@ _SIGNATURES = {
     "sgk_discounted_returns": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_double]),
     "sgk_discount_powers": (ctypes.c_int, [ctypes.c_double, ctypes.c_int32, _V]),
     "sgk_discounted_returns_members": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _V]),
+    "sgk_members_select": (ctypes.c_int, [_V, _V, ctypes.c_int32, ctypes.c_int32, _V, ctypes.POINTER(SgkMembersExplore)]),
+    "sgk_members_clone": (ctypes.c_int, [_V, _V, ctypes.c_int32, ctypes.POINTER(SgkMembersTensor), ctypes.c_int32, _V]),
+    "sgk_members_select_host": (ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V]),
+    "sgk_members_explore_pick": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "sgk_copy_boards": (ctypes.c_int, [_V, _V]),
     "sgk_copy_step_records": (ctypes.c_int, [_V, _V]),
     "sgk_copy_episode_state": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V]),

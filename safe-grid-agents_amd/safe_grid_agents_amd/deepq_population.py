@@ -24,6 +24,7 @@ from . import _lib
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
 from .member_hyper import DQN_NAMES, resolve, validate_values
 from .metering import BatchMetrics
+from .pbt import PBTMixin
 from .ppo_population import FUSED_CELLS, _as_i64, default_member_seed
 
 # BatchedDeepQAgent.Q's parameters (state_dict keys, registration order) and the short names of the stacked tensors
@@ -52,7 +53,7 @@ def unstack_state_dict(stacked, m):
     return {key: stacked[name][m].detach().clone() for key, name in zip(MEMBER_KEYS, PARAMS)}
 
 
-class BatchedDeepQPopulation:
+class BatchedDeepQPopulation(PBTMixin):
     """M independent DeepQAgents over env's N = M x E envs (see the module docstring).
 
     args: the deep-q flags (lr, discount, batch_size, sync_every, epsilon, epsilon_anneal, n_layers, n_hidden, seed). member_seeds:
@@ -69,8 +70,11 @@ class BatchedDeepQPopulation:
     The annealed values are computed ON THE DEVICE, once per step(): three elementwise float64 kernels evaluate update_epsilon's
     expression 1.0 - (1 - eps0) * t / anneal for every member in its own order of operations (IEEE double: the host's bits), so
     step() makes no host synchronisation and no host-to-device copy. set_member_hyper copies into these tensors: the kernels and
-    any recorded graph keep their addresses."""
+    any recorded graph keep their addresses.
 
+    exploit_explore (PBTMixin) perturbs lr and discount (the learner row's columns); the three epsilon tensors are cloned only."""
+
+    PBT_COLUMNS = DQN_NAMES[:2]
     torch = torch  # (the two BatchedDeepQAgent methods borrowed below read self.torch)
     build_Q = BatchedDeepQAgent.build_Q
 
@@ -175,6 +179,23 @@ class BatchedDeepQPopulation:
         out["loss"] = self.loss
         return out
 
+    def pbt_tensors(self):
+        """Every per-member tensor the learner or the acting reads or updates: what a clone takes from its source (exploit_explore).
+        The epsilon tensors exist with member_hyper only."""
+        out = (list(self.cur.values()) + list(self.cur_t.values()) + list(self.target.values()) + list(self.target_t.values())
+               + self.adam_m + self.adam_v + self.adam_vmax + [self.step_count])
+        if self.hyper is not None:
+            out += [self.hyper["epsilon0"], self._one_minus_eps0, self.hyper["epsilon"]]
+        return out
+
+    def _pbt_pull_extra(self):
+        return self.hyper["epsilon0"]
+
+    def _pbt_after_pull(self, rows, extra):
+        self.member_values["lr"], self.member_values["discount"] = [r[0] for r in rows], [r[1] for r in rows]
+        self.member_values["epsilon"] = list(extra)
+        self._eps_t = None  # (derived from the epsilon tensors: evaluated again at the next step)
+
     def _member_index(self, m):
         m = int(m)
         if not 0 <= m < self.n_members:
@@ -202,6 +223,7 @@ class BatchedDeepQPopulation:
         """{name: member m's value} for lr, discount, epsilon (the shared values without member_hyper): what the `args` of the single
         agent that member m equals carry."""
         m = self._member_index(m)
+        self._pull_if_dirty()
         if self.member_values is None:
             return {"lr": self.lr, "discount": self.discount, "epsilon": self.eps0}
         return {k: self.member_values[k][m] for k in DQN_NAMES}
@@ -219,6 +241,7 @@ class BatchedDeepQPopulation:
         if hyper is not None:
             if self.hyper is None:
                 raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+            self._pull_if_dirty()
             for name, value in dict(hyper).items():
                 if name not in DQN_NAMES:
                     raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(DQN_NAMES)))

@@ -849,6 +849,35 @@ class BatchedGridworldEnv:
         """The device pointer of a float64 [n_members, n_fields] tensor: rows of sgk_ppo_member_hyper (4) / sgk_dqn_member_hyper (2)."""
         return ctypes.c_void_p(self._check(member_hyper, "member_hyper", shape=(int(n_members), n_fields), dtypes=("float64",)).data_ptr())
 
+    def members_select(self, scores, n_replace, src_out, explore=None):
+        """Truncation selection over a population in ONE launch of one workgroup (sgk_members_select): scores float64 [M] on this
+        device -> src_out int32 [M], the member each member becomes (itself, unless it is one of the n_replace worst). explore: a
+        filled _lib.SgkMembersExplore (the perturbed hyper rows are written by the same launch), or None. No allocation, no host
+        synchronisation: the call can be recorded in a graph."""
+        M = int(scores.shape[0]) if hasattr(scores, "shape") and len(scores.shape) == 1 else -1
+        self._check(scores, "scores", shape=(M,), dtypes=("float64",))
+        self._check(src_out, "src_out", shape=(M,), dtypes=("int32",))
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_members_select(self._h.ptr, ctypes.c_void_p(scores.data_ptr()), M, int(n_replace),
+                                               ctypes.c_void_p(src_out.data_ptr()), None if explore is None else ctypes.byref(explore)))
+        self._sync_lib_to_torch()
+
+    def members_clone(self, src, descs, status):
+        """Every member d with src[d] != d becomes a copy of member src[d] over the stacked tensors `descs` describes, in ONE launch per
+        64 descriptors (sgk_members_clone). src int32 [M] and status int32 [1] on this device; descs: a ctypes array of
+        _lib.SgkMembersTensor (pbt.tensor_descs builds it from tensors [M, ...] and keeps them alive). No allocation, no host
+        synchronisation."""
+        M = int(src.shape[0])
+        self._check(src, "src", shape=(M,), dtypes=("int32",))
+        self._check(status, "status", numel=1, dtypes=("int32",))
+        self._sync_torch_to_lib()
+        for i in range(0, len(descs), _lib.MEMBERS_MAX_TENSORS):
+            n = min(_lib.MEMBERS_MAX_TENSORS, len(descs) - i)
+            part = ctypes.cast(ctypes.addressof(descs) + i * ctypes.sizeof(_lib.SgkMembersTensor), ctypes.POINTER(_lib.SgkMembersTensor))
+            _lib.check(self.lib.sgk_members_clone(self._h.ptr, ctypes.c_void_p(src.data_ptr()), M, part, n,
+                                                  ctypes.c_void_p(status.data_ptr())))
+        self._sync_lib_to_torch()
+
     def ppo_epochs_members(self, learner, n_members, member_keys=None, member_hyper=None):
         """One PPO learn() call of n_members independent PPOMLPAgents in ONE HIP launch (sgk_ppo_epochs_members); `learner` is a filled
         _lib.SgkPpoLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None.

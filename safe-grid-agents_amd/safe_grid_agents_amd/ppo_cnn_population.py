@@ -130,6 +130,10 @@ class BatchedPPOCNNPopulation(PPOMemberHyper):
         out["step"] = self.step
         return out
 
+    def pbt_tensors(self):
+        """Every per-member tensor the learner or the acting reads or updates: what a clone takes from its source (exploit_explore)."""
+        return list(self.cur.values()) + self.adam_m + self.adam_v + list(self.old.values()) + [self.step]
+
     def load_member(self, m, state_dict, hyper=None):
         """Member m's current weights <- a PPOCNNAgent state dict (its own parameters; `old_policy.*` keys, when present, give the old
         policy, else the old policy is left alone until the next sync()). hyper: {name: value}, member m's hyper-parameters (a

@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from .member_hyper import PPO_NAMES, resolve, validate_values
 from .metering import BatchMetrics
+from .pbt import PBTMixin
 from .ppo import PPOMLPAgent
 
 # PPOMLPAgent's own parameters (state_dict keys, registration order) and the short names of the stacked tensors
@@ -75,18 +76,35 @@ def _as_i64(values):
     return [v - 2 ** 64 if v >= 2 ** 63 else v for v in (int(x) & _MASK for x in values)]
 
 
-class PPOMemberHyper:
+class PPOMemberHyper(PBTMixin):
     """The per-member hyper-parameters of the two PPO populations (BatchedPPOPopulation, BatchedPPOCNNPopulation).
 
     member_hyper=None: `hyper` is None and the population calls the shared-hyper entry points, exactly as without this class.
     Else `member_values` holds {name: [M floats]} for all of PPO_NAMES on the host and `hyper` the device tensors the kernels read:
       hyper["learner"]    float64 [M, 4], rows of sgk_ppo_member_hyper (lr, clipping, critic_coeff, entropy_bonus)
+      hyper["discount"]   float64 [M], the members' discounts: no kernel reads it; it travels with a clone (exploit_explore), since the
+                          float32 power table cannot be re-derived on the device bit for bit, and feeds pull_member_hyper
       hyper["gamma_pow"]  float32 [M, T], row m = float32(discount_m ** t): the table of sgk_discounted_returns_members, made at the
                           first gather_rollout for its horizon T (absent before)
-    set_member_hyper copies into them, so the kernels and any recorded graph keep their addresses and see the new values."""
+    set_member_hyper copies into them, so the kernels and any recorded graph keep their addresses and see the new values.
+
+    exploit_explore (PBTMixin) perturbs the learner row's four columns; the discount -- its value and its row of every cached power
+    table -- is cloned only."""
 
     hyper = None
     member_values = None
+    PBT_COLUMNS = PPO_NAMES[:4]
+
+    def _pbt_hyper_tensors(self):
+        return [self.hyper["discount"]] + [self._gamma[T] for T in sorted(self._gamma)]
+
+    def _pbt_pull_extra(self):
+        return self.hyper["discount"]
+
+    def _pbt_after_pull(self, rows, extra):
+        for k, name in enumerate(PPO_NAMES[:4]):
+            self.member_values[name] = [row[k] for row in rows]
+        self.member_values["discount"] = list(extra)
 
     def _resolve_member_hyper(self, args, member_hyper, n_members):
         """Validation only (no device): ValueError for an unknown name, a wrong length, an invalid value."""
@@ -98,7 +116,8 @@ class PPOMemberHyper:
         if self.member_values is not None:
             v, self._gamma = self.member_values, {}
             rows = [[v[k][m] for k in PPO_NAMES[:4]] for m in range(self.n_members)]
-            self.hyper = {"learner": torch.tensor(rows, dtype=torch.float64, device=self.device)}
+            self.hyper = {"learner": torch.tensor(rows, dtype=torch.float64, device=self.device),
+                          "discount": torch.tensor(v["discount"], dtype=torch.float64, device=self.device)}
 
     def set_member_hyper(self, name, values):
         """Member m's `name` <- values[m] (validated: ValueError), copied INTO the device tensors (no new allocation): the next
@@ -111,6 +130,7 @@ class PPOMemberHyper:
         vals = validate_values(name, values, self.n_members)
         self.member_values[name] = vals
         if name == "discount":
+            self.hyper["discount"].copy_(torch.tensor(vals, dtype=torch.float64))
             for T, table in self._gamma.items():
                 table.copy_(self._gamma_host(T))
         else:
@@ -120,6 +140,7 @@ class PPOMemberHyper:
         """{name: member m's value} for all of PPO_NAMES (the shared values without member_hyper): what the `args` of the single agent
         that member m equals carry."""
         m = self._member_index(m)
+        self._pull_if_dirty()
         if self.member_values is None:
             return {"lr": self.lr, "clipping": self.clipping, "critic_coeff": self.critic_coeff, "entropy_bonus": self.entropy_bonus,
                     "discount": self.discount}
@@ -138,6 +159,7 @@ class PPOMemberHyper:
             return
         if self.hyper is None:
             raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
+        self._pull_if_dirty()
         for name, value in dict(hyper).items():
             if name not in PPO_NAMES:
                 raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(PPO_NAMES)))
@@ -156,6 +178,7 @@ class PPOMemberHyper:
             return None
         T = int(T)
         if T not in self._gamma:
+            self._pull_if_dirty()  # (the new table's rows come from the host mirror)
             self._gamma[T] = self._gamma_host(T).to(self.device)
         self.hyper["gamma_pow"] = self._gamma[T]
         return self._gamma[T]
@@ -252,6 +275,10 @@ class BatchedPPOPopulation(PPOMemberHyper):
         out.update({"v_" + k: t for k, t in zip(PARAMS, self.adam_v)})
         out["step"] = self.step
         return out
+
+    def pbt_tensors(self):
+        """Every per-member tensor the learner or the acting reads or updates: what a clone takes from its source (exploit_explore)."""
+        return list(self.cur.values()) + list(self.cur_t.values()) + self.adam_m + self.adam_v + [self.step] + list(self.old.values())
 
     def load_member(self, m, state_dict, hyper=None):
         """Member m's current weights <- a PPOMLPAgent state dict (its own parameters; `old_policy.*` keys, when present, give the old

@@ -15,6 +15,7 @@ from .agents import AGENT_MAP
 from .loops import EVAL_MAP, LEARN_MAP, WARMUP_MAP
 from .member_hyper import parse_sweep, point_label, sweep_member_hyper, sweep_table
 from .metering import NullWriter, make_meters
+from .pbt import parse_pbt
 
 ENV_MAP = _envs.ENV_MAP
 
@@ -44,6 +45,13 @@ _CORE_FLAGS = [
     # as replica m // G of it (member_hyper.parse_sweep). Names: lr, clipping, critic_coeff, entropy_bonus, discount (ppo-*); lr,
     # discount, epsilon (deep-q).
     ("sweep", "W", dict(action="append", default=None, metavar="NAME=v1,v2,...")),
+    # extension: with --members, `--pbt-every K` runs population-based training: after every K-th training period the worst
+    # --pbt-fraction of the members (by that period's return) become copies of the best, the --pbt-perturb hyper-parameters of the
+    # copies multiplied by one of the two --pbt-factors (pbt.PBTMixin.exploit_explore). A --sweep then only gives the starting values.
+    ("pbt-every", "PE", dict(type=int, default=0)),
+    ("pbt-fraction", "PF", dict(type=float, default=None)),
+    ("pbt-factors", "PX", dict(type=str, default=None, metavar="down,up")),
+    ("pbt-perturb", "PP", dict(type=str, default=None, metavar="name,name")),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -64,6 +72,11 @@ _PPO_FLAGS = [_LR,
 _MEMBERS = ("members", "M", dict(type=int, default=argparse.SUPPRESS))
 # --sweep likewise (`... ppo-mlp -l 1e-3 -r 4 -e 2 --members 6 --sweep lr=1e-3,1e-2 --sweep clipping=0.1,0.2,0.5`)
 _SWEEP = ("sweep", "W", dict(action="append", default=argparse.SUPPRESS, metavar="NAME=v1,v2,..."))
+# --pbt-* likewise
+_PBT = [("pbt-every", "PE", dict(type=int, default=argparse.SUPPRESS)),
+        ("pbt-fraction", "PF", dict(type=float, default=argparse.SUPPRESS)),
+        ("pbt-factors", "PX", dict(type=str, default=argparse.SUPPRESS, metavar="down,up")),
+        ("pbt-perturb", "PP", dict(type=str, default=argparse.SUPPRESS, metavar="name,name"))]
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -81,9 +94,9 @@ _AGENT_FLAGS = {
                ("q-body", "qb", dict(type=str, default="mlp", choices=("mlp", "cnn"),
                                      help="mlp: the reference's network (default, pinned); cnn: non-parity conv body, -N only")),
                ("n-channels", "ch", dict(type=int, default=5)),
-               _MEMBERS, _SWEEP],
-    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP],
-    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP],
+               _MEMBERS, _SWEEP] + _PBT,
+    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP] + _PBT,
+    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP] + _PBT,
 }
 
 
@@ -194,6 +207,10 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         members_n_envs(args)  # ppo-mlp, ppo-cnn: N = M x rollouts; deep-q: -N, a multiple of M
     sweep = sweep_grid(args)  # --sweep: (names, grid) or None; SystemExit for a sweep that cannot run
     member_hyper = sweep_member_hyper(sweep[0], sweep[1], members) if sweep else None
+    pbt = parse_pbt(args)  # --pbt-every: {"every", "fraction", "factors", "perturb"} or None; SystemExit for flags that cannot run
+    if pbt:
+        member_hyper = member_hyper or {}  # (every member starts from args' values; the per-member tensors exist all the same)
+        sweep = None  # the grid only gave the starting values: after a PBT step member m is no longer "point m % G"
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -297,6 +314,12 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         if deepq and agent.last_loss is not None:
             loss = agent.last_loss.mean() if members else agent.last_loss.reshape(-1)[0]  # (a population: the members' mean)
             writer.add_scalar("Train/value_loss", float(loss), agent.t)
+        if pbt and episode % pbt["every"] == 0:  # the score: this period's per-member return (member_metrics, reset every period)
+            agent.exploit_explore(fraction=pbt["fraction"], perturb=pbt["perturb"], factors=pbt["factors"])
+            writer.add_scalar("Train/pbt/replaced", int((agent.pbt_src.cpu().numpy() != np.arange(members)).sum()), episode)
+            for name in agent.PBT_COLUMNS:
+                values = np.array([agent.member_hyper_of(m)[name] for m in range(members)], dtype=np.float64)
+                writer.add_histogram("Train/pbt/%s" % name, values, episode)
         reporter(hidden_reward=bm.meter("safeties")["avg"], obs_reward=bm.meter("returns")["avg"])
         # evaluation cadence exactly as the reference's loops decide it: whiler (tabular-q / deep-q, learn.py:21-22) evaluates
         # after the episodes with episode % eval_every == eval_every - 1; ppo_learn (learn.py:100) after those with
@@ -315,6 +338,12 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         for line in sweep_table(sweep[0], sweep[1], [m.meter("returns")["avg"] for m in per_member],
                                 [m.meter("safeties")["avg"] for m in per_member]):
             print(line)
+    if pbt and per_member is not None and rank == 0:  # one line per member: where its hyper-parameters ended, and its last return
+        print("#### PBT: %d members, every %d periods the worst %d became the best; values and return of the last training period ####"
+              % (members, pbt["every"], int(pbt["fraction"] * members)))
+        for m in range(members):
+            print("member %-4d %-60s return %10.4f" % (m, " ".join("%s=%g" % kv for kv in agent.member_hyper_of(m).items()),
+                                                       per_member[m].meter("returns")["avg"]))
     return agent, env
 
 
