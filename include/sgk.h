@@ -769,6 +769,41 @@ SGK_API int sgk_policy_rollout_members_eps(sgk_env *h, const sgk_mlp_weights *w,
                                            uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev,
                                            const double *member_epsilon_dev);
 
+/* ---- a population as ONE agent: every member acts on every env, then the members vote ------------------------------------------
+ * The calls above are block-diagonal (member m acts in its own n_envs / n_members envs). sgk_policy_act_members_all is the cross
+ * product, n_members policies x all n_envs envs in one launch: entry [m][e] of member_actions_out_dev (uint8 [n_members][n_envs]) is
+ * member m's GREEDY action on env e's current board -- PPOBaseAgent.act (reference policy_base.py:47-52: the argmax of the policy) or
+ * DeepQAgent.act (value.py:89-92: the argmax of the Q-values) of the m-th agent: sgk_policy_act with epsilon = 0 and the m-th slice of
+ * the weight tensors, which are stacked on a leading member axis as for sgk_policy_rollout_members (`w` addresses member 0). The first
+ * maximum wins; no random number is drawn. member_scores_out_dev: float32 [n_members][n_envs][4], 16-byte aligned, the four scores
+ * behind every action, or NULL. Actions and scores of member m are BIT-IDENTICAL to those of sgk_policy_act(epsilon 0) called with
+ * member m's slices (the same kernel body; a workgroup serves one member for the whole launch, stages that member's weights once and
+ * walks the env tiles of 128; the grid is workgroups-per-member x n_members). The env state is read, never written; no allocation, no
+ * host synchronisation, legal inside a stream capture. Shapes: sgk_policy_act's (the levels the fused policy kernel covers, n_hidden
+ * in {64, 100, 128}). SGK_ERR_INVALID for a NULL pointer, n_members outside 1 .. 4096, another n_hidden, a scores pointer that is not
+ * 16-byte aligned (all checked before the handle is looked at), a NULL handle and a level without the kernel. */
+SGK_API int sgk_policy_act_members_all(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, uint8_t *member_actions_out_dev,
+                                       float *member_scores_out_dev);
+/* The plurality vote over member_actions_dev (uint8 [n_members][n_envs], what sgk_policy_act_members_all wrote), one lane per env:
+ * votes[a] = the number of voters whose action is a; the env's action is the first a with the largest count (ties go to the lowest
+ * index: np.argmax). The voters are all members (member_ids_dev NULL; n_voters 0 or n_members) or the n_voters members listed in
+ * member_ids_dev (int32 [n_voters] in device memory, 1 <= n_voters <= n_members; e.g. the top k of a score, no weights are copied). An
+ * id outside 0 .. n_members - 1 and an action byte above 3 cast no vote; the ids are not checked for duplicates (a member listed
+ * twice votes twice). actions_out_dev: uint8 [n_envs], the argument sgk_step takes next; votes_out_dev: uint16 [n_envs][4], 8-byte
+ * aligned, or NULL. dissent_dev: int64 [2] in device memory, 8-byte aligned, or NULL; ACCUMULATED, not overwritten (zero it before the
+ * first call): [0] += voters - votes[action], [1] += voters, summed over the envs whose episode is NOT over (the state word's flag,
+ * read when the kernel runs). Two integers, so disagreement = dissent[0] / dissent[1] is exact. No allocation, no host
+ * synchronisation, legal inside a stream capture. SGK_ERR_INVALID (nothing is launched or written) for a NULL member_actions_dev or
+ * actions_out_dev, n_members outside 1 .. 4096, n_voters outside the ranges above, a misaligned votes_out_dev or dissent_dev; all
+ * checked before the handle is looked at. */
+SGK_API int sgk_members_vote(sgk_env *h, const uint8_t *member_actions_dev, int32_t n_members, const int32_t *member_ids_dev,
+                             int32_t n_voters, uint8_t *actions_out_dev, uint16_t *votes_out_dev, int64_t *dissent_dev);
+/* sgk_members_vote on the host, from host arrays (the same counting and tie rule, compiled for the host): no handle, no device.
+ * member_actions: uint8 [n_members][n_envs]; live: uint8 [n_envs], non-zero = the env counts towards dissent, or NULL (every env
+ * does). SGK_ERR_INVALID as sgk_members_vote, and for n_envs < 0. */
+SGK_API int sgk_members_vote_host(const uint8_t *member_actions, int32_t n_members, int64_t n_envs, const int32_t *member_ids,
+                                  int32_t n_voters, const uint8_t *live, uint8_t *actions_out, uint16_t *votes_out, int64_t *dissent);
+
 /* ---- PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186), batched ------------------------------ */
 /* rewards_dev / returns_dev: float32 [n_trajectories][t_max] row-major; lengths_dev: int32 [n_trajectories] or NULL
  * (every trajectory t_max long). returns[i][t] = sum_{k >= t} float32(discount ** k) * rewards[i][k], accumulated left

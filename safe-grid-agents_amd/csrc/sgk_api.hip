@@ -819,6 +819,25 @@ int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t draw_index,
   return SGK_OK;
 } SGK_CATCH_STATUS
 
+int sgk_policy_act_members_all(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, uint8_t *member_actions_out_dev,
+                               float *member_scores_out_dev) try {
+  // (the arguments first: the refusals need no handle and no device)
+  if (!w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3) return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: NULL weights");
+  if (!member_actions_out_dev) return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: member_actions_out_dev is NULL");
+  if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
+    return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (n_members < 1 || n_members > SGK_MEMBERS_MAX)
+    return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: n_members must be in 1..%d (got %d)", SGK_MEMBERS_MAX, (int)n_members);
+  if (member_scores_out_dev && ((uintptr_t)member_scores_out_dev & 15u))
+    return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: member_scores_out_dev must be 16-byte aligned");
+  SGK_CHECK_HANDLE(h);
+  if (!sgk::mlp_cells_have_kernel(h->sh.n_cells))
+    return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: the fused policy kernel does not cover boards of %d cells", h->sh.n_cells);
+  sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
+  SGK_HIP(sgk::launch_policy_act_members(h->sh, pw, n_members, member_actions_out_dev, member_scores_out_dev, h->stream));
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 // sgk_policy_rollout (one member) and sgk_policy_rollout_members: the same checks, the same kernel
 static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, int32_t mode, double epsilon, uint64_t draw_index0,
                                int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,

@@ -85,6 +85,10 @@ struct PolicyWeights {
 // mode 0: epsilon-greedy over the scores (DeepQAgent.act_explore); mode 1: Categorical(logits = scores).sample() (PPO)
 hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, uint8_t *actions, float *scores, double eps,
                              uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
+// the cross product (sgk_policy_act_members_all): `w` addresses member 0 of weight tensors stacked [n_members][...]; member m's greedy
+// action on EVERY env -> member_actions [n_members][n], its scores -> member_scores [n_members][n][4] or null
+hipError_t launch_policy_act_members(const Shard &sh, const PolicyWeights &w, int n_members, uint8_t *member_actions, float *member_scores,
+                                     hipStream_t st);
 // n_steps of {forward, draw, env.step} in one launch; trajectory outputs optional ([n_steps][n]...); SGK_F_AUTO_RESET in flags.
 // n_members > 1: `w` addresses member 0 of weight tensors stacked [n_members][...], member m acts in the envs m * n / n_members ..;
 // member_metrics: int64 [n_members][SGK_METRICS_LEN] each member's episodes are also booked in, or null
@@ -259,6 +263,9 @@ struct MembersCloneArgs {
 hipError_t launch_members_select(const double *scores, int n_members, int n_replace, int32_t *src_out, const MembersExplore *explore,
                                  hipStream_t st);
 hipError_t launch_members_clone(const Shard &sh, const MembersCloneArgs &a, hipStream_t st);
+// the plurality vote over member_actions [n_members][n] (sgk_members_vote): ids [n_voters] or null (voter i is member i)
+hipError_t launch_members_vote(const Shard &sh, const uint8_t *member_actions, int n_members, const int32_t *ids, int n_voters,
+                               uint8_t *actions_out, uint16_t *votes_out, int64_t *dissent, hipStream_t st);
 
 int host_random_action(uint64_t seed, uint64_t env, uint64_t t);  // sgk_host_debug.cpp
 int host_debug_transition(const SgkRules &R, int agent_cell, int box_cell, int action, int out[5]);

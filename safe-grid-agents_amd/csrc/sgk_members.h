@@ -33,4 +33,23 @@ SGK_HD double members_perturb(double v, double f, double lo, double hi) {
   return p > hi ? hi : p;
 }
 
+// ---- the ensemble's vote (include/sgk.h: sgk_members_vote; the kernel and sgk_members_vote_host run this) -------------------------------
+// One env's four counts in one 64-bit word, 16 bits per action, action 0 lowest: SGK_MEMBERS_MAX = 4096 voters fit, and the word is
+// the env's row of votes_out as it lies in memory. A byte that is no action (> 3) casts no vote.
+SGK_HD uint64_t members_vote_cast(uint64_t counts, uint32_t action) { return action < 4u ? counts + (1ull << (16u * action)) : counts; }
+SGK_HD uint32_t members_vote_count(uint64_t counts, int action) { return (uint32_t)(counts >> (16 * action)) & 0xffffu; }
+SGK_HD uint32_t members_vote_total(uint64_t counts) {
+  return members_vote_count(counts, 0) + members_vote_count(counts, 1) + members_vote_count(counts, 2) + members_vote_count(counts, 3);
+}
+// the first action with the most votes: np.argmax's tie rule
+SGK_HD int members_vote_winner(uint64_t counts) {
+  int best = 0;
+  uint32_t most = members_vote_count(counts, 0);
+  for (int a = 1; a < 4; ++a) {
+    const uint32_t c = members_vote_count(counts, a);
+    if (c > most) most = c, best = a;
+  }
+  return best;
+}
+
 }  // namespace sgk

@@ -4,11 +4,15 @@
 //                          optionally, writes the replaced members' perturbed hyper-parameter rows (the explore step)
 //   members_clone_kernel   grid (chunks, n_members): the workgroups of a replaced member copy its source's slabs over its own, tensor
 //                          by tensor, from descriptors that arrive as kernel arguments
+// and the ensemble's vote (sgk_members_vote) over the [n_members][n_envs] actions of sgk_policy_act_members_all (sgk_policy.hip):
+//   members_vote_kernel    one lane per env counts the voters' action bytes, names the first action with the most votes and adds the
+//                          live envs' dissent to two global counters
 // The arithmetic both sides of the C-ABI share (the order, the coin, the perturbed value) is sgk_members.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
+#include "sgk_device.h"
 #include "sgk_host_core.h"
 #include "sgk_kernels.h"
 #include "sgk_members.h"
@@ -22,6 +26,7 @@ namespace {
 constexpr int SELECT_WG = 1024;
 constexpr int SELECT_PER_LANE = SGK_MEMBERS_MAX / SELECT_WG;  // members a lane ranks at most (the kernel is instantiated for 1, 2 and 4)
 constexpr int CLONE_WG = 256;
+constexpr int VOTE_WG = 256;
 
 // One workgroup. LDS: the scores (32 KB) and the order (16 KB) of up to 4096 members. A lane ranks the members tid, tid + 1024, ...
 // in ONE pass over the scores (every lane reads the same score: an LDS broadcast), scatters order[rank] = member, and after the
@@ -112,6 +117,39 @@ __global__ __launch_bounds__(CLONE_WG) void members_clone_kernel(const MembersCl
   }
 }
 
+// One lane per env, grid-stride. Voter i is member ids[i] (null: member i) -- wave-uniform, so the voter loop's only vector load is the
+// action byte: row m of member_actions [n_members][n] is contiguous across the lanes (64 bytes a wave). An id outside 0 .. n_members - 1
+// casts no vote. The four counts travel as one word (sgk_members.h) and are stored as the env's 8-byte row of votes_out. dissent gains
+// {voters that did not vote for the winner, votes cast} over the envs whose episode is not over: per-lane sums, a wavefront reduction
+// after the loop, then one atomic instruction per wave (lane c adds counter c) -- skipped by a wave whose envs were all over.
+__global__ __launch_bounds__(VOTE_WG) void members_vote_kernel(const uint8_t *__restrict__ member_actions, int n_members,
+                                                               const int32_t *__restrict__ ids, int n_voters, int64_t n,
+                                                               const uint64_t *__restrict__ state, uint8_t *__restrict__ actions_out,
+                                                               uint64_t *__restrict__ votes_out, unsigned long long *__restrict__ dissent) {
+  long long lost = 0, cast = 0;
+  for (int64_t env = (int64_t)blockIdx.x * VOTE_WG + threadIdx.x; env < n; env += (int64_t)gridDim.x * VOTE_WG) {
+    uint64_t counts = 0;
+#pragma unroll 4
+    for (int i = 0; i < n_voters; ++i) {
+      const int m = ids ? ids[i] : i;
+      if ((unsigned)m < (unsigned)n_members) counts = members_vote_cast(counts, member_actions[(size_t)m * (size_t)n + (size_t)env]);
+    }
+    const int winner = members_vote_winner(counts);
+    actions_out[env] = (uint8_t)winner;
+    if (votes_out) votes_out[env] = counts;
+    if (dissent && !unpack_state(state[env]).over) {
+      const uint32_t total = members_vote_total(counts);
+      lost += total - members_vote_count(counts, winner);
+      cast += total;
+    }
+  }
+  if (!dissent) return;  // (uniform: a kernel argument)
+  lost = wave_sum64(lost);
+  cast = wave_sum64(cast);
+  const int c = threadIdx.x & 63;
+  if (c < 2 && cast > 0) atomicAdd(&dissent[c], (unsigned long long)(c == 0 ? lost : cast));
+}
+
 }  // namespace
 
 hipError_t launch_members_select(const double *scores, int n_members, int n_replace, int32_t *src_out, const MembersExplore *explore,
@@ -144,6 +182,16 @@ hipError_t launch_members_clone(const Shard &sh, const MembersCloneArgs &a, hipS
   return hipGetLastError();
 }
 
+hipError_t launch_members_vote(const Shard &sh, const uint8_t *member_actions, int n_members, const int32_t *ids, int n_voters,
+                               uint8_t *actions_out, uint16_t *votes_out, int64_t *dissent, hipStream_t st) {
+  (void)hipGetLastError();
+  const int grid = grid_for((sh.n + VOTE_WG - 1) / VOTE_WG, sh.max_grid);
+  members_vote_kernel<<<dim3(grid), dim3(VOTE_WG), 0, st>>>(member_actions, n_members, ids, n_voters, sh.n, sh.state, actions_out,
+                                                            reinterpret_cast<uint64_t *>(votes_out),
+                                                            reinterpret_cast<unsigned long long *>(dissent));
+  return hipGetLastError();
+}
+
 }  // namespace sgk
 
 // ---- the C-ABI ---------------------------------------------------------------------------------------------------------------------
@@ -157,6 +205,22 @@ static int check_select(const double *scores, int32_t n_members, int32_t n_repla
   if (n_replace < 0 || n_replace > n_members / 2)
     return fail(SGK_ERR_INVALID, "%s: n_replace must be in 0..n_members / 2 = %d (got %d): the replaced and their sources are disjoint",
                 who, (int)(n_members / 2), (int)n_replace);
+  return SGK_OK;
+}
+
+// sgk_members_vote and sgk_members_vote_host: the voters are all members (ids NULL, n_voters 0 or n_members) or the n_voters listed
+static int check_vote(const uint8_t *member_actions, int32_t n_members, const int32_t *ids, int32_t n_voters, const uint8_t *actions_out,
+                      const uint16_t *votes_out, const char *who) {
+  if (!member_actions) return fail(SGK_ERR_INVALID, "%s: member_actions is NULL", who);
+  if (!actions_out) return fail(SGK_ERR_INVALID, "%s: actions_out is NULL", who);
+  if (n_members < 1 || n_members > SGK_MEMBERS_MAX)
+    return fail(SGK_ERR_INVALID, "%s: n_members must be in 1..%d (got %d)", who, SGK_MEMBERS_MAX, (int)n_members);
+  if (!ids && n_voters != 0 && n_voters != n_members)
+    return fail(SGK_ERR_INVALID, "%s: without member_ids every member votes: n_voters must be 0 or n_members = %d (got %d)", who,
+                (int)n_members, (int)n_voters);
+  if (ids && (n_voters < 1 || n_voters > n_members))
+    return fail(SGK_ERR_INVALID, "%s: n_voters must be in 1..n_members = %d (got %d)", who, (int)n_members, (int)n_voters);
+  if ((uintptr_t)votes_out & 7u) return fail(SGK_ERR_INVALID, "%s: votes_out must be 8-byte aligned (one env's four counts are stored at once)", who);
   return SGK_OK;
 }
 
@@ -234,6 +298,45 @@ int sgk_members_select_host(const double *scores, int32_t n_members, int32_t n_r
     order[rank] = m;
   }
   for (int r = 0; r < M; ++r) src_out[order[r]] = r >= M - n_replace ? order[M - 1 - r] : order[r];
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
+int sgk_members_vote(sgk_env *h, const uint8_t *member_actions_dev, int32_t n_members, const int32_t *member_ids_dev, int32_t n_voters,
+                     uint8_t *actions_out_dev, uint16_t *votes_out_dev, int64_t *dissent_dev) try {
+  // (the arguments first: the refusals need no handle and no device)
+  if (int rc = check_vote(member_actions_dev, n_members, member_ids_dev, n_voters, actions_out_dev, votes_out_dev, "sgk_members_vote")) return rc;
+  if ((uintptr_t)dissent_dev & 7u) return fail(SGK_ERR_INVALID, "sgk_members_vote: dissent_dev must be 8-byte aligned");
+  const sgk::Shard *sh;
+  hipStream_t st;
+  if (int rc = sgk_handle_launch_site(h, &sh, &st)) return rc;
+  SGK_HIP(sgk::launch_members_vote(*sh, member_actions_dev, n_members, member_ids_dev, member_ids_dev ? n_voters : n_members, actions_out_dev,
+                                   votes_out_dev, dissent_dev, st));
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
+int sgk_members_vote_host(const uint8_t *member_actions, int32_t n_members, int64_t n_envs, const int32_t *member_ids, int32_t n_voters,
+                          const uint8_t *live, uint8_t *actions_out, uint16_t *votes_out, int64_t *dissent) try {
+  if (int rc = check_vote(member_actions, n_members, member_ids, n_voters, actions_out, votes_out, "sgk_members_vote_host")) return rc;
+  if (n_envs < 0) return fail(SGK_ERR_INVALID, "sgk_members_vote_host: n_envs < 0");
+  const int voters = member_ids ? n_voters : n_members;
+  long long lost = 0, cast = 0;
+  for (int64_t env = 0; env < n_envs; ++env) {
+    uint64_t counts = 0;
+    for (int i = 0; i < voters; ++i) {
+      const int m = member_ids ? member_ids[i] : i;
+      if ((unsigned)m < (unsigned)n_members) counts = sgk::members_vote_cast(counts, member_actions[(size_t)m * (size_t)n_envs + (size_t)env]);
+    }
+    const int winner = sgk::members_vote_winner(counts);
+    actions_out[env] = (uint8_t)winner;
+    if (votes_out)
+      for (int a = 0; a < 4; ++a) votes_out[env * 4 + a] = (uint16_t)sgk::members_vote_count(counts, a);
+    if (dissent && (!live || live[env])) {
+      const uint32_t total = sgk::members_vote_total(counts);
+      lost += total - sgk::members_vote_count(counts, winner);
+      cast += total;
+    }
+  }
+  if (dissent) dissent[0] += lost, dissent[1] += cast;
   return SGK_OK;
 } SGK_CATCH_STATUS
 

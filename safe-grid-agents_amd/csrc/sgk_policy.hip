@@ -166,7 +166,13 @@ __device__ __forceinline__ __attribute__((ext_vector_type(4))) float policy_forw
   return mine;
 }
 
-template <int K0, int H, int MODE>
+// MEMBERS = true (sgk_policy_act_members_all; MODE 0): the cross product, every member's greedy action on every env. The grid is
+// (workgroups per member, n_members); the workgroup serves member blockIdx.y for the whole launch -- the weight pointers address member 0
+// of tensors stacked [n_members][...] and are moved to the member's slices here, the outputs are [n_members][n](, [4]) and are moved to the
+// member's rows -- and its grid-stride loop over ALL n envs' tiles runs along x, as in the shared kernel. The member's actions are greedy
+// (epsilon 0: select_action's argmax, no Philox block; the launcher passes no epsilon / draw pointers). Everything else is the same
+// code, so member m's scores and actions are the bytes the MEMBERS = false kernel leaves for member m's slices and epsilon 0.
+template <int K0, int H, int MODE, bool MEMBERS = false>
 __global__ __launch_bounds__(PMFMA_WG) void policy_mfma_kernel(const int8_t *__restrict__ boards, int pitch,
                                                                const float *__restrict__ w1t, const float *__restrict__ b1,
                                                                const float *__restrict__ w2, const float *__restrict__ b2,
@@ -176,6 +182,19 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_mfma_kernel(const int8_t *__r
                                                                uint64_t draw, const double *__restrict__ eps_ptr,
                                                                const uint64_t *__restrict__ draw_ptr) {
   typedef PolicyMfmaGeom<K0, H> G;
+  static_assert(MODE == 0 || !MEMBERS, "the members' actions are greedy");
+  if constexpr (MEMBERS) {
+    const size_t member = blockIdx.y;
+    w1t += member * (K0 * H);
+    b1 += member * H;
+    w2 += member * (H * H);
+    b2 += member * H;
+    w3t += member * (H * 4);
+    b3 += member * 4;
+    actions += member * (size_t)n;
+    if (scores_out) scores_out += member * (size_t)n * 4;
+    eps = 0.0;
+  }
   constexpr int MT = G::MT, KS1 = G::KS1, NT = PMFMA_NT;
   typedef float f4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) unsigned char policy_smem[];
@@ -286,7 +305,8 @@ __global__ __launch_bounds__(PMFMA_WG) void policy_mfma_kernel(const int8_t *__r
     const int64_t env = env0 + wave_env + (lane & 31);  // the env whose action this lane (of lanes 0..31) picks at the end
     double u;
     uint32_t x2;
-    draw_block<MODE>(env_base + (uint64_t)env, draw, seed, u, x2);  // VALU work in the shadow of the MFMAs below
+    if constexpr (MEMBERS) u = 1.0, x2 = 0;  // (never below epsilon 0: the greedy action)
+    else draw_block<MODE>(env_base + (uint64_t)env, draw, seed, u, x2);  // VALU work in the shadow of the MFMAs below
     const f4 mine = policy_forward<K0, H>(lw1, lw2, lw3, lb1, lb2, lb3, tile, wave_env, lane, [&]() {
       if (t == (int64_t)blockIdx.x) {  // first pass: W2 / W3 have arrived by now
 #pragma unroll
@@ -564,6 +584,40 @@ hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, 
     }
   });
 #undef SGK_POLICY_LAUNCH
+  if (le != hipSuccess) return le;
+  return hipGetLastError();
+}
+
+// A member's workgroups: one per 128-env tile while all members' fit the CUs, at least one -- launch_policy_rollout's rule. With it the
+// launch takes what policy_mfma_kernel takes on n_members x n envs with ONE weight set, 0.97 - 1.05 x from 16 x 2 048 to 256 x 32 768
+// (profiles/ensemble/kernel_trace.log): staging a member's weights per workgroup does not show.
+static int policy_act_members_wgs(const Shard &sh, int n_members) {
+  return grid_for((sh.n + PMFMA_ENVS - 1) / PMFMA_ENVS, std::max(sh.n_cus / n_members, 1));
+}
+
+template <int K0, int HID>
+static hipError_t launch_act_members(const Shard &sh, const PolicyWeights &w, int n_members, uint8_t *actions, float *scores, hipStream_t st) {
+  constexpr size_t lds = PolicyMfmaGeom<K0, HID>::lds_bytes;
+  hipError_t ae = allow_dynamic_lds<policy_mfma_kernel<K0, HID, 0, true>>(sh.device, (int)lds);
+  if (ae != hipSuccess) return ae;
+  policy_mfma_kernel<K0, HID, 0, true><<<dim3(policy_act_members_wgs(sh, n_members), n_members), dim3(PMFMA_WG), lds, st>>>(
+      sh.boards, sh.pitch, w.w1t, w.b1, w.w2, w.b2, w.w3t, w.b3, actions, scores, sh.n, 0.0, (uint64_t)0, (uint64_t)0, (uint64_t)0, nullptr,
+      nullptr);
+  return hipSuccess;
+}
+
+hipError_t launch_policy_act_members(const Shard &sh, const PolicyWeights &w, int n_members, uint8_t *member_actions, float *member_scores,
+                                     hipStream_t st) {
+  (void)hipGetLastError();
+  if (n_members < 1 || n_members > SGK_MEMBERS_MAX) return hipErrorInvalidValue;
+  hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
+  SGK_DISPATCH_CELLS(sh.n_cells, {
+    switch (w.n_hidden) {
+    case 64: le = launch_act_members<K0, 64>(sh, w, n_members, member_actions, member_scores, st); break;
+    case 100: le = launch_act_members<K0, 100>(sh, w, n_members, member_actions, member_scores, st); break;
+    case 128: le = launch_act_members<K0, 128>(sh, w, n_members, member_actions, member_scores, st); break;
+    }
+  });
   if (le != hipSuccess) return le;
   return hipGetLastError();
 }

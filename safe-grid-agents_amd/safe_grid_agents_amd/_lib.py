@@ -204,6 +204,9 @@ _SIGNATURES = {
                                                   ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V]),
     "sgk_policy_rollout_members_eps": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                                       ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V, _V]),
+    "sgk_policy_act_members_all": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, _V, _V]),
+    "sgk_members_vote": (ctypes.c_int, [_V, _V, ctypes.c_int32, _V, ctypes.c_int32, _V, _V, _V]),
+    "sgk_members_vote_host": (ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
     "sgk_discounted_returns": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_double]),
     "sgk_discount_powers": (ctypes.c_int, [ctypes.c_double, ctypes.c_int32, _V]),
     "sgk_discounted_returns_members": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _V]),

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
+from .ensemble import EnsembleMixin
 from .member_hyper import DQN_NAMES, resolve, validate_values
 from .metering import BatchMetrics
 from .pbt import PBTMixin
@@ -53,8 +54,9 @@ def unstack_state_dict(stacked, m):
     return {key: stacked[name][m].detach().clone() for key, name in zip(MEMBER_KEYS, PARAMS)}
 
 
-class BatchedDeepQPopulation(PBTMixin):
-    """M independent DeepQAgents over env's N = M x E envs (see the module docstring).
+class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
+    """M independent DeepQAgents over env's N = M x E envs (see the module docstring). ensemble_act() / evaluate_ensemble()
+    (ensemble.EnsembleMixin) let the M Q-networks act as one agent on all N envs: every member votes on every env.
 
     args: the deep-q flags (lr, discount, batch_size, sync_every, epsilon, epsilon_anneal, n_layers, n_hidden, seed). member_seeds:
     member m's initial weights are what BatchedDeepQAgent.build_Q gives on the CPU under torch.manual_seed(member_seeds[m]), Q first,
@@ -296,6 +298,8 @@ class BatchedDeepQPopulation(PBTMixin):
         """The stacked Q-networks in the members rollout's layout (the kernels keep w1t / w3t current)."""
         c = self.cur
         return {"w1t": self.cur_t["w1t"], "b1": c["b1"], "w2": c["w2"], "b2": c["b2"], "w3t": self.cur_t["w3t"], "b3": c["b3"]}
+
+    _ensemble_weights = greedy_weights  # (EnsembleMixin: the population's own tensors, their addresses stay)
 
     def evaluate(self, eval_timesteps):
         """batched_default_eval (reference eval.py:8-56) for every member's Q-network, greedy: its two phases as two launches of the

@@ -845,6 +845,55 @@ class BatchedGridworldEnv:
             (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
         self._sync_lib_to_torch()
 
+    def policy_act_members_all(self, weights, n_members, out=None, scores_out=None):
+        """Every member's GREEDY action on EVERY env's current board in ONE HIP launch (sgk_policy_act_members_all): the cross product
+        the ensemble votes over. `weights` stacked on a leading member axis (see _member_weights_arg); returns uint8 [n_members, N]
+        (`out` when given), row m what policy_act(member m's slices, epsilon=0.0) gives, bit for bit; scores_out: float32
+        [n_members, N, 4] on this device that receives the scores, or None. The envs are not touched."""
+        import torch
+
+        n_members = int(n_members)
+        if not 1 <= n_members <= _lib.MEMBERS_MAX:
+            raise ValueError("n_members must be in 1..%d, not %d" % (_lib.MEMBERS_MAX, n_members))
+        w = self._member_weights_arg(weights, n_members)
+        if out is None:
+            out = torch.empty((n_members, self.n_envs), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._check(out, "out", shape=(n_members, self.n_envs), dtypes=("uint8",))
+        sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(n_members, self.n_envs, 4),
+                                                                         dtypes=("float32",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_policy_act_members_all(self._h.ptr, ctypes.byref(w), n_members, ctypes.c_void_p(out.data_ptr()), sp))
+        self._sync_lib_to_torch()
+        return out
+
+    def members_vote(self, member_actions, members=None, out=None, votes_out=None, dissent=None):
+        """The plurality vote per env over member_actions, uint8 [M, N] on this device (what policy_act_members_all returns), in ONE
+        HIP launch (sgk_members_vote): returns uint8 [N] (`out` when given), the first action with the most votes. members: int32 [k]
+        on this device, 1 <= k <= M, the members that vote (an index outside 0 .. M - 1 casts no vote), or None: all. votes_out: uint16
+        (or int16) [N, 4] that receives the counts; dissent: int64 [2] that GAINS (voters that did not vote for the winner, votes
+        cast) over the envs whose episode is not over; both on this device, or None."""
+        if not hasattr(member_actions, "shape") or len(member_actions.shape) != 2:
+            raise ValueError("member_actions must be a uint8 tensor [n_members, %d]" % self.n_envs)
+        M = int(member_actions.shape[0])
+        if not 1 <= M <= _lib.MEMBERS_MAX:
+            raise ValueError("member_actions holds %d members; the vote takes 1..%d" % (M, _lib.MEMBERS_MAX))
+        self._check(member_actions, "member_actions", shape=(M, self.n_envs), dtypes=("uint8",))
+        ip, k = None, 0
+        if members is not None:
+            k = int(members.shape[0]) if hasattr(members, "shape") and len(members.shape) == 1 else -1
+            if not 1 <= k <= M:
+                raise ValueError("members must be an int32 tensor of 1..%d member indices" % M)
+            ip = ctypes.c_void_p(self._check(members, "members", shape=(k,), dtypes=("int32",)).data_ptr())
+        out = self._out_actions(out)
+        vp = None if votes_out is None else ctypes.c_void_p(self._check(votes_out, "votes_out", shape=(self.n_envs, 4),
+                                                                        dtypes=("uint16", "int16")).data_ptr())
+        dp = None if dissent is None else ctypes.c_void_p(self._check(dissent, "dissent", shape=(2,), dtypes=("int64",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_members_vote(self._h.ptr, ctypes.c_void_p(member_actions.data_ptr()), M, ip, k,
+                                             ctypes.c_void_p(out.data_ptr()), vp, dp))
+        self._sync_lib_to_torch()
+        return out
+
     def _member_hyper_arg(self, member_hyper, n_members, n_fields):
         """The device pointer of a float64 [n_members, n_fields] tensor: rows of sgk_ppo_member_hyper (4) / sgk_dqn_member_hyper (2)."""
         return ctypes.c_void_p(self._check(member_hyper, "member_hyper", shape=(int(n_members), n_fields), dtypes=("float64",)).data_ptr())

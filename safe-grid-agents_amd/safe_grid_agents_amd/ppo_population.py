@@ -21,6 +21,7 @@ import types
 import torch
 
 from . import _lib
+from .ensemble import EnsembleMixin
 from .member_hyper import PPO_NAMES, resolve, validate_values
 from .metering import BatchMetrics
 from .pbt import PBTMixin
@@ -184,8 +185,9 @@ class PPOMemberHyper(PBTMixin):
         return self._gamma[T]
 
 
-class BatchedPPOPopulation(PPOMemberHyper):
-    """M independent PPOMLPAgents over env's N = M x E envs (see the module docstring).
+class BatchedPPOPopulation(EnsembleMixin, PPOMemberHyper):
+    """M independent PPOMLPAgents over env's N = M x E envs (see the module docstring). ensemble_act() / evaluate_ensemble()
+    (ensemble.EnsembleMixin) let the M members act as one agent on all N envs: every member votes on every env.
 
     args: the ppo-mlp flags (lr, discount, batch_size, epochs, clipping, entropy_bonus, critic_coeff, n_layers, n_hidden, seed).
     member_seeds: member m's initial weights are those of PPOMLPAgent(env, args) built under torch.manual_seed(member_seeds[m])
@@ -245,6 +247,7 @@ class BatchedPPOPopulation(PPOMemberHyper):
         self._metrics_init = self._metrics_init.to(dev)
         self.draws = 0  # lockstep act_explore calls so far == the RNG draw index
         self._buffers = None
+        self._ens_w3t = None
         self._refresh_transposes()
         self.sync()
         self.reset_member_metrics()
@@ -342,6 +345,15 @@ class BatchedPPOPopulation(PPOMemberHyper):
         c = self.cur
         return {"w1t": self.cur_t["w1t"], "b1": c["b1"], "w2": c["w2"], "b2": c["b2"], "w3t": c["wa"].transpose(1, 2).contiguous(),
                 "b3": c["ba"]}
+
+    def _ensemble_weights(self):
+        """_greedy_weights() at addresses that stay (EnsembleMixin records launches): the actor head's transpose is copied into one
+        buffer, made at the first call."""
+        c = self.cur
+        if self._ens_w3t is None:
+            self._ens_w3t = torch.empty_like(self.old["w3t"])
+        self._ens_w3t.copy_(c["wa"].transpose(1, 2))
+        return {"w1t": self.cur_t["w1t"], "b1": c["b1"], "w2": c["w2"], "b2": c["b2"], "w3t": self._ens_w3t, "b3": c["ba"]}
 
     def gather_rollout(self, cheat=False, horizon=None):
         """PPOBaseAgent.gather_rollout (reference policy_base.py:133-177) of every member at once: one episode per env under its

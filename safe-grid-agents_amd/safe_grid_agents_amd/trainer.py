@@ -12,6 +12,7 @@ import numpy as np
 
 from . import envs as _envs
 from .agents import AGENT_MAP
+from .ensemble import check_ensemble_eval, write_ensemble_eval
 from .loops import EVAL_MAP, LEARN_MAP, WARMUP_MAP
 from .member_hyper import parse_sweep, point_label, sweep_member_hyper, sweep_table
 from .metering import NullWriter, make_meters
@@ -52,6 +53,9 @@ _CORE_FLAGS = [
     ("pbt-fraction", "PF", dict(type=float, default=None)),
     ("pbt-factors", "PX", dict(type=str, default=None, metavar="down,up")),
     ("pbt-perturb", "PP", dict(type=str, default=None, metavar="name,name")),
+    # extension: with --members on ppo-mlp or deep-q, `--ensemble-eval` follows every evaluation with one of the ENSEMBLE: all members
+    # act on every env and their plurality vote is the action (ensemble.EnsembleMixin.evaluate_ensemble)
+    ("ensemble-eval", "EN", dict(action="store_true")),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -77,6 +81,8 @@ _PBT = [("pbt-every", "PE", dict(type=int, default=argparse.SUPPRESS)),
         ("pbt-fraction", "PF", dict(type=float, default=argparse.SUPPRESS)),
         ("pbt-factors", "PX", dict(type=str, default=argparse.SUPPRESS, metavar="down,up")),
         ("pbt-perturb", "PP", dict(type=str, default=argparse.SUPPRESS, metavar="name,name"))]
+# --ensemble-eval likewise (with ppo-cnn it parses and stops the run with a message: ensemble.check_ensemble_eval)
+_ENSEMBLE = ("ensemble-eval", "EN", dict(action="store_true", default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -94,9 +100,9 @@ _AGENT_FLAGS = {
                ("q-body", "qb", dict(type=str, default="mlp", choices=("mlp", "cnn"),
                                      help="mlp: the reference's network (default, pinned); cnn: non-parity conv body, -N only")),
                ("n-channels", "ch", dict(type=int, default=5)),
-               _MEMBERS, _SWEEP] + _PBT,
-    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP] + _PBT,
-    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP] + _PBT,
+               _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
+    "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
+    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
 }
 
 
@@ -211,6 +217,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     if pbt:
         member_hyper = member_hyper or {}  # (every member starts from args' values; the per-member tensors exist all the same)
         sweep = None  # the grid only gave the starting values: after a PBT step member m is no longer "point m % G"
+    ensemble = {} if check_ensemble_eval(args) else None  # --ensemble-eval: the last ensemble evaluation's figures; SystemExit if it cannot run
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if getattr(args, "devices", 1) > 1 and world != args.devices:
@@ -329,9 +336,9 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         else:
             eval_next = episode % args.eval_every == args.eval_every - 1
         if agent is not None and eval_next:
-            period = _batched_eval(agent, env, args, writer, period, rank, sdist)
+            period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble)
     if agent is not None:  # train.py:81: one more evaluation after the loop, unconditionally (also when the last episode had one)
-        period = _batched_eval(agent, env, args, writer, period, rank, sdist)
+        period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble)
     if sweep and per_member is not None and rank == 0:  # the table, once: the last training period's episodes
         print("#### SWEEP: %d grid points x %d replicas, return and safety of the last training period, mean +- std over replicas ####"
               % (len(sweep[1]), members // len(sweep[1])))
@@ -344,6 +351,9 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         for m in range(members):
             print("member %-4d %-60s return %10.4f" % (m, " ".join("%s=%g" % kv for kv in agent.member_hyper_of(m).items()),
                                                        per_member[m].meter("returns")["avg"]))
+    if ensemble and rank == 0:  # one line: the last evaluation of the members voting on every env
+        print("#### ENSEMBLE: %d members vote on every env; last evaluation: return %.4f safety %.4f disagreement %.4f (%d of %d votes) ####"
+              % (members, ensemble["return"], ensemble["safety"], ensemble["disagreement"], ensemble["dissent"], ensemble["votes"]))
     return agent, env
 
 
@@ -380,7 +390,7 @@ def members_n_envs(args):
     return n
 
 
-def _batched_eval(agent, env, args, writer, period, rank, sdist):
+def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None):
     from .loops import batched_default_eval
 
     if rank == 0:
@@ -392,5 +402,14 @@ def _batched_eval(agent, env, args, writer, period, rank, sdist):
     else:
         batched_default_eval(agent, env, args.eval_timesteps)
     sdist.global_metrics(env).write(writer, period, prefix="Evaluation/")
+    if ensemble is not None:
+        # --ensemble-eval: the same schedule once more with the members' vote as the agent. Training does not notice it: greedy acting
+        # draws nothing and leaves the members' weights, optimiser state, metrics and draw counters alone; the env's metrics vector is
+        # reset by the next training period before it is read, and the env.reset() below -- which follows every evaluation -- puts the
+        # envs back to their initial states. (Levels whose own draws are keyed by the env's reset count see more resets, as they do
+        # after any evaluation.)
+        bm, dissent = agent.evaluate_ensemble(args.eval_timesteps)
+        write_ensemble_eval(writer, bm, dissent, period)
+        ensemble.update(dissent, **{"return": bm.meter("returns")["avg"], "safety": bm.meter("safeties")["avg"]})
     env.reset()
     return period + 1
