@@ -379,6 +379,33 @@ SGK_API int sgk_tabq_copy_table(sgk_tabq *q, int64_t env_begin, int64_t env_coun
 SGK_API int sgk_tabq_global_step(const sgk_tabq *q, int64_t *t_out);
 SGK_API double sgk_tabq_epsilon(double epsilon, int64_t epsilon_anneal, int64_t t); /* epsilon in force at global step t */
 
+/* ---- the consensus of the N private agents: a plurality vote per state (csrc/sgk_tabq_consensus.hip) ---------------------------
+ * One streaming read of the tables ([n_states][n_envs][4] float64, 32 * n_states * n_envs bytes). The rule, exactly:
+ *  - agent e votes in state s iff it may (voters_mask: mask[e] != 0; NULL: every agent) and its row of s has an entry that compares
+ *    != 0.0. A row the agent never learnt is all zeros -- the reference's fresh defaultdict row (value.py:31) -- and its argmax of 0
+ *    is not an opinion; -0.0 counts as zero;
+ *  - a voter's action is the library's own greedy rule, sgk_tabq_act(explore = 0): the first maximum, as np.argmax picks.
+ * The counts are integers: the result depends neither on the grid's shape nor on the order of the atomics. The outputs are
+ * OVERWRITTEN (the caller need not zero them). No allocation, no host synchronisation, enqueued on the handle's stream: capturable in
+ * a hipGraph. Levels with hashed tables (SGK_TOMATO_WATERING) are refused with SGK_ERR_INVALID: an agent's slots are its own, so the
+ * agents' rows do not line up by state. A NULL handle and NULL outputs are SGK_ERR_INVALID. The tables, the agent step counter and
+ * epsilon are only read; like sgk_tabq_table_dev, the call makes the per-step kernels re-read the one row per env they keep (the
+ * table is written through, so they read the same values again).
+ * votes_out_dev  int64 [n_states][4]  votes_out[s][a] = number of voting agents whose greedy action in state s is a
+ * voters_out_dev int64 [n_states]     number of voting agents in state s (= sum over a of votes_out[s][a]); may be NULL
+ * voters_mask_dev uint8 [n_envs] or NULL: agent e may vote iff mask[e] != 0 (NULL: every agent) */
+SGK_API int sgk_tabq_consensus(sgk_tabq *q, const uint8_t *voters_mask_dev, int64_t *votes_out_dev, int64_t *voters_out_dev);
+/* every agent's table := table_dev (float64 [n_states][4], device); the kept per-env rows are invalidated (as by
+ * sgk_tabq_invalidate_rows: a host-side flag raised when the call is MADE -- behind a replay of a recorded call, the caller raises it).
+ * One streaming write of the same bytes; no allocation, no host synchronisation, the handle's stream. The agent step counter and
+ * epsilon stay. Hashed levels, a NULL handle and a NULL table are SGK_ERR_INVALID. */
+SGK_API int sgk_tabq_load_shared(sgk_tabq *q, const double *table_dev);
+/* the vote on host arrays: table_host [n_agents][n_states][4] as sgk_tabq_copy_table hands it out; no GPU, no handle. The same rule
+ * (the same code) as sgk_tabq_consensus. A NULL table or votes_out and a negative count are SGK_ERR_INVALID; voters_out_host and the
+ * mask may be NULL. */
+SGK_API int sgk_tabq_consensus_host(const double *table_host, int64_t n_agents, int64_t n_states, const uint8_t *voters_mask_host,
+                                    int64_t *votes_out_host, int64_t *voters_out_host);
+
 /* ---- DeepQAgent.act_explore, batched (reference value.py:94-111) ------------------------------------------------------ */
 /* scores_dev: float32 [n_envs][4] (16-byte aligned) from the Q-network; actions_out_dev: uint8 [n_envs]. Draws from
  * Categorical(eps/4 + (1 - eps) on the argmax) with the counter RNG (Philox stream 2, keyed by global env index and

@@ -4,6 +4,7 @@ default log dir runs/<env>/<agent>/<baseline|corrupt>/<seed>."""
 import os
 import random
 
+from .consensus import check_consensus_eval
 from .ensemble import check_ensemble_eval
 from .pbt import parse_pbt
 from .trainer import members_n_envs, prepare_parser, sweep_grid, train, train_batched
@@ -32,6 +33,7 @@ def main(argv=None):
     parse_pbt(args)  # --pbt-*: stops here when it cannot run (no --members, an agent without a population, a bad fraction / factor / name)
     sweep_grid(args)  # --sweep: stops here, with the valid names, when it cannot run (no --members, an unknown name, M % G != 0)
     check_ensemble_eval(args)  # --ensemble-eval: stops here when it cannot run (no --members, a population without the ensemble)
+    check_consensus_eval(args)  # --consensus-eval: stops here when it cannot run (not tabular-q, tomato, -N < 2, more than one device)
     if getattr(args, "devices", 1) > 1 and "WORLD_SIZE" not in os.environ:
         if getattr(args, "n_envs", 0) <= 0:
             raise SystemExit("--devices shards the batched trainer: give -N/--n-envs too")

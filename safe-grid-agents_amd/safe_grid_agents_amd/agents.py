@@ -17,6 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
+from .consensus import ConsensusMixin
 
 
 # ---- mixins (reference base.py:5-47) ---------------------------------------------------------------
@@ -227,7 +228,7 @@ class DeepQAgent(_EpsilonMixin, BaseActor, BaseLearner, BaseExplorer):
 
 
 # ---- batched tabular Q on the GPU -------------------------------------------------------------------
-class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
+class BatchedTabularQAgent(ConsensusMixin, BaseActor, BaseLearner, BaseExplorer):
     """N private TabularQAgents (one per env of a BatchedGridworldEnv), tables float64 in HBM, state-major: [n_states][N][4]
     (table() / table_host() present them agent by agent, [N][n_states][4]).
 
@@ -235,6 +236,9 @@ class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
     dictionary key (flattened board) becomes a perfect-hash state index (agent cell, or agent cell x box cell);
     exploration draws come from the counter RNG (Philox stream 1: one 53-bit uniform + one action per step), so
     parity with the CPU restatement is stated on that stream, not on numpy's Mersenne Twister.
+
+    consensus() / load_shared_table() / consensus_agent() / evaluate_consensus() (consensus.ConsensusMixin): what the N agents,
+    taken together, recommend in every state -- a plurality vote over the tables on the device.
     """
 
     fused_eval = True  # loops.batched_default_eval hands the evaluation to evaluate(); False: its loop of per-step calls (A/B)
@@ -243,6 +247,7 @@ class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
         import torch
 
         self.env = env
+        self.args = args  # (consensus_agent() makes its agent from them)
         self.lib = env.lib
         self.action_n = env.action_space.n
         self.lr, self.discount = float(args.lr), float(args.discount)
@@ -261,6 +266,7 @@ class BatchedTabularQAgent(BaseActor, BaseLearner, BaseExplorer):
         self._actions = torch.empty(env.n_envs, dtype=torch.uint8, device="cuda:%d" % env.device)
 
     def close(self):
+        self._close_consensus()  # evaluate_consensus()'s agents and their envs
         if getattr(self, "_h", None):
             self.lib.sgk_tabq_destroy(self._h)
             self._h = None

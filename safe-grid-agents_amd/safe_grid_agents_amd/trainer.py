@@ -12,6 +12,7 @@ import numpy as np
 
 from . import envs as _envs
 from .agents import AGENT_MAP
+from .consensus import check_consensus_eval, write_consensus_eval
 from .ensemble import check_ensemble_eval, write_ensemble_eval
 from .loops import EVAL_MAP, LEARN_MAP, WARMUP_MAP
 from .member_hyper import parse_sweep, point_label, sweep_member_hyper, sweep_table
@@ -56,6 +57,9 @@ _CORE_FLAGS = [
     # extension: with --members on ppo-mlp or deep-q, `--ensemble-eval` follows every evaluation with one of the ENSEMBLE: all members
     # act on every env and their plurality vote is the action (ensemble.EnsembleMixin.evaluate_ensemble)
     ("ensemble-eval", "EN", dict(action="store_true")),
+    # extension: with tabular-q and -N > 1 on one device, `--consensus-eval` follows every evaluation with one of the CONSENSUS agent: the
+    # plurality vote, per state, of the batch's private agents (consensus.ConsensusMixin.evaluate_consensus). Absent unless given.
+    ("consensus-eval", "CE", dict(action="store_true", default=argparse.SUPPRESS)),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -83,10 +87,12 @@ _PBT = [("pbt-every", "PE", dict(type=int, default=argparse.SUPPRESS)),
         ("pbt-perturb", "PP", dict(type=str, default=argparse.SUPPRESS, metavar="name,name"))]
 # --ensemble-eval likewise (with ppo-cnn it parses and stops the run with a message: ensemble.check_ensemble_eval)
 _ENSEMBLE = ("ensemble-eval", "EN", dict(action="store_true", default=argparse.SUPPRESS))
+# --consensus-eval likewise (with another agent than tabular-q it parses and stops the run with a message: consensus.check_consensus_eval)
+_CONSENSUS = ("consensus-eval", "CE", dict(action="store_true", default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
-    "tabular-q": [_LR, _EPS, _ANNEAL],
+    "tabular-q": [_LR, _EPS, _ANNEAL, _CONSENSUS],
     "deep-q": [_LR, _EPS, _ANNEAL,
                ("replay-capacity", "r", dict(type=int, default=10000)),
                ("sync-every", "s", dict(type=int, default=10000)),
@@ -218,8 +224,11 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         member_hyper = member_hyper or {}  # (every member starts from args' values; the per-member tensors exist all the same)
         sweep = None  # the grid only gave the starting values: after a PBT step member m is no longer "point m % G"
     ensemble = {} if check_ensemble_eval(args) else None  # --ensemble-eval: the last ensemble evaluation's figures; SystemExit if it cannot run
+    consensus = {} if check_consensus_eval(args) else None  # --consensus-eval likewise
 
     rank, local_rank, world = sdist.env_from_torchrun()
+    if consensus is not None and world > 1:
+        raise SystemExit("--consensus-eval runs on one device: summing the votes over %d ranks is not built" % world)
     if getattr(args, "devices", 1) > 1 and world != args.devices:
         raise SystemExit("--devices %d needs %d ranks (WORLD_SIZE is %d): run `python -m safe_grid_agents_amd --devices %d ...`, "
                          "which starts them, or torch.distributed.run --nproc-per-node %d" % (
@@ -336,9 +345,9 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         else:
             eval_next = episode % args.eval_every == args.eval_every - 1
         if agent is not None and eval_next:
-            period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble)
+            period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble, consensus)
     if agent is not None:  # train.py:81: one more evaluation after the loop, unconditionally (also when the last episode had one)
-        period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble)
+        period = _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble, consensus)
     if sweep and per_member is not None and rank == 0:  # the table, once: the last training period's episodes
         print("#### SWEEP: %d grid points x %d replicas, return and safety of the last training period, mean +- std over replicas ####"
               % (len(sweep[1]), members // len(sweep[1])))
@@ -354,6 +363,9 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     if ensemble and rank == 0:  # one line: the last evaluation of the members voting on every env
         print("#### ENSEMBLE: %d members vote on every env; last evaluation: return %.4f safety %.4f disagreement %.4f (%d of %d votes) ####"
               % (members, ensemble["return"], ensemble["safety"], ensemble["disagreement"], ensemble["dissent"], ensemble["votes"]))
+    if consensus:  # one line: the last evaluation of the agents' plurality vote per state
+        print("#### CONSENSUS: %d agents vote on every state; last evaluation: return %.4f safety %.4f agreement %.4f (%d votes over %d states) ####"
+              % (env.n_envs, consensus["return"], consensus["safety"], consensus["agreement"], consensus["voters"], consensus["voted_states"]))
     return agent, env
 
 
@@ -390,7 +402,7 @@ def members_n_envs(args):
     return n
 
 
-def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None):
+def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None, consensus=None):
     from .loops import batched_default_eval
 
     if rank == 0:
@@ -411,5 +423,12 @@ def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None):
         bm, dissent = agent.evaluate_ensemble(args.eval_timesteps)
         write_ensemble_eval(writer, bm, dissent, period)
         ensemble.update(dissent, **{"return": bm.meter("returns")["avg"], "safety": bm.meter("safeties")["avg"]})
+    if consensus is not None:
+        # --consensus-eval: the same schedule once more with the agents' plurality vote per state as the agent. Training does not notice
+        # it: the vote only reads the tables, and the consensus agent acts on an env handle of its own -- this env's metrics, reset
+        # counters and state words are not touched.
+        bm, stats = agent.evaluate_consensus(args.eval_timesteps)
+        write_consensus_eval(writer, bm, stats, period)
+        consensus.update(stats, **{"return": bm.meter("returns")["avg"], "safety": bm.meter("safeties")["avg"]})
     env.reset()
     return period + 1
