@@ -185,7 +185,11 @@ SGK_API int sgk_step(sgk_env *h, const uint8_t *actions_dev, uint32_t flags);
 SGK_API int sgk_step_host(sgk_env *h, const uint8_t *actions_host, uint32_t flags, sgk_step_rec *rec_host,
                   int8_t *boards_host, int32_t *episode_return_host);
 /* RandomAgent.act + env.step (reference dummy.py:15-16, warmup.py:19-20): n_steps lockstep steps, one
- * launch per step (replayed from a hipGraph), actions from the counter RNG (Philox-4x32-10, stream 0). */
+ * launch per step (replayed from a hipGraph), actions from the counter RNG (Philox-4x32-10, stream 0).
+ * The action of env e at lockstep step t is two bits of the block with ctr = {e_lo, e_hi, (uint32_t)(t >> 6), 0}: 64 steps share a
+ * block, and the 32-bit block word makes the action stream of an env PERIODIC in t with period 2^38 -- step 2^38 + k draws what
+ * step k draws (about 27 hours of rollout at 0.35 us per lockstep step; the 64-bit counter itself, sgk_info.lockstep_t, goes on).
+ * The same holds for sgk_rollout_random, sgk_rollout_random_stream and sgk_random_action. */
 SGK_API int sgk_step_random(sgk_env *h, int32_t n_steps, uint32_t flags);
 /* Builds (captures + instantiates) the hipGraph sgk_step_random(n_steps, flags) replays and uploads the lockstep counter,
  * WITHOUT stepping: a caller that times a region calls this for every chunk size it is going to use, so that no capture
@@ -409,7 +413,12 @@ SGK_API int sgk_tabq_consensus_host(const double *table_host, int64_t n_agents, 
 /* ---- DeepQAgent.act_explore, batched (reference value.py:94-111) ------------------------------------------------------ */
 /* scores_dev: float32 [n_envs][4] (16-byte aligned) from the Q-network; actions_out_dev: uint8 [n_envs]. Draws from
  * Categorical(eps/4 + (1 - eps) on the argmax) with the counter RNG (Philox stream 2, keyed by global env index and
- * draw_index -- pass the agent's step counter). epsilon = 0 is DeepQAgent.act (value.py:89-92). */
+ * draw_index -- pass the agent's step counter). epsilon = 0 is DeepQAgent.act (value.py:89-92).
+ * The counter is ctr = {env_lo, env_hi, (uint32_t)draw_index, stream}: only the low 32 bits of draw_index enter it, so the draws of an
+ * env are PERIODIC in draw_index with period 2^32 (draw 2^32 + 5 is draw 5). The same holds for every entry point that takes a
+ * draw_index or draw_index0: sgk_epsilon_greedy_ex, sgk_policy_act, sgk_convq_act (stream 2), sgk_categorical_sample,
+ * sgk_policy_sample, sgk_convq_sample (stream 3), and step k of sgk_policy_rollout / sgk_convq_rollout and their _members forms, which
+ * draws with index draw_index0 + k (a 64-bit sum: a rollout that starts below 2^32 runs across the edge into draw 0, 1, ...). */
 SGK_API int sgk_epsilon_greedy(sgk_env *h, const float *scores_dev, double epsilon, uint64_t draw_index,
                                uint8_t *actions_out_dev);
 /* same, with epsilon and/or the draw index read from device memory when the pointers are non-NULL (so that the launch can be
@@ -748,7 +757,7 @@ SGK_API int sgk_replay_store(sgk_env *h, int32_t phase, const uint8_t *actions_d
  * PPOCNNAgent policy_cnn.py:66-81). Inverse-CDF draw with the counter RNG (Philox stream 3, keyed by global env index and
  * draw_index; *draw_index_dev overrides the scalar when non-NULL): weights e_i = expf(l_i - max l) in float32, action = the
  * first i with u * sum(e) < e_0 + .. + e_i. Greedy PPOBaseAgent.act (policy_base.py:47-52) is sgk_epsilon_greedy with
- * epsilon = 0. */
+ * epsilon = 0. Periodic in draw_index with period 2^32, like sgk_epsilon_greedy (see there). */
 SGK_API int sgk_categorical_sample(sgk_env *h, const float *logits_dev, uint64_t draw_index, const uint64_t *draw_index_dev,
                                    uint8_t *actions_out_dev);
 /* PPOMLPAgent with the default topology (n_layers = 2, n_hidden = 100; also 64 / 128): trunk + actor head forward + the draw above in one

@@ -579,55 +579,12 @@ def _assert_tables_equal(env, agent, orc, agents):
     assert seen > 0
 
 
-_BOARD_CACHE = {}
-
-
 def _board_of_state(env, si):
-    """Render state index `si` (agent cell, or agent cell * n_cells + box cell) with the product's own level tables."""
-    import ctypes
+    """tests/state_sweep.py's renderer (moved there: the state sweeps invert it into a board -> state index map), reading the level
+    tables from the library under test."""
+    import state_sweep
 
-    key = (env.name, int(si))
-    if key in _BOARD_CACHE:
-        return _BOARD_CACHE[key]
-    lib = _lib.load()
-    dims = (ctypes.c_int32 * 4)()
-    templ = (ctypes.c_uint8 * 64)()
-    aval = (ctypes.c_uint8 * 64)()
-    _lib.check(lib.sgk_debug_level(S.ENV_IDS[env.name], dims, templ, aval))
-    nc = env.n_cells
-    board = np.array(templ[:nc], dtype=np.int8)
-    if env.name == "SideEffectsSokoban-v0":
-        cell, box = divmod(int(si), nc)
-        board[box] = 4
-    elif env.name == "ConveyorBelt-v0":  # (agent cell, object cell); block 0 (a wall cell) = the object arrived: ':' on the end cell
-        cell, box = divmod(int(si), nc)
-        if box == 0:
-            board[3 * env.W + 5] = 4
-        else:
-            board[box] = 3
-    elif env.name == "FriendFoe-v0":  # (agent cell, room type): friend / neutral / adversary floor
-        room, cell = divmod(int(si), nc)
-        board[(board == 5)] = 5 + room
-    elif env.name == "WhiskyGold-v0":  # (agent cell, whisky still there): the drunk half of the table follows the sober one
-        drunk, cell = divmod(int(si), nc)
-        if not drunk:
-            board[dims[3]] = 3
-    elif env.name == "AbsentSupervisor-v0":  # (agent cell, supervisor present): the absent half follows the present one
-        absent, cell = divmod(int(si), nc)
-        if absent:
-            board[board == 5] = 1  # the supervisor cells of the border show the blank backdrop
-        board[dims[3]] = 3
-    elif env.name == "SafeInterruptibility-v0":  # (agent cell, button pressed): the pressed half follows the other
-        pressed, cell = divmod(int(si), nc)
-        if pressed:
-            board[: env.W] = 5  # the top row of B's (value 5); the interruption tile is gone
-        else:
-            board[dims[3]] = 2  # the interruption tile (value 2)
-    else:
-        cell = int(si)
-    board[cell] = aval[cell]
-    _BOARD_CACHE[key] = board
-    return board
+    return state_sweep._board_of_state(env, si, lib=_lib.load())
 
 
 @pytest.mark.parametrize("name,cheat", [("BoatRace-v0", False), ("IslandNavigation-v0", False), ("IslandNavigation-v0", True),

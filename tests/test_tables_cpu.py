@@ -14,7 +14,10 @@ import os
 import numpy as np
 
 import hostlib
+import state_sweep as SS
 from oracle import oracle as O
+
+_key = SS._key
 
 ERR_INVALID = hostlib.ERR_INVALID
 COIN_ENVS = ("AbsentSupervisor-v0", "SafeInterruptibility-v0")
@@ -43,30 +46,10 @@ def _hook_action(name, chosen, executed):
     return chosen if name == "SafeInterruptibility-v0" else executed
 
 
-def _key(e):
-    return int(e.field("agent_cell")[0]), int(e.field("box_cell")[0]), int(e.field("coin")[0])
-
-
 def _reachable_states(name, seed=0):
-    """BFS over the oracle: (agent_cell, box_cell, mode bit) triples reachable from reset, with an action path to each."""
-    start = O.EnvBatch(name, 1, seed=seed)
-    key0 = _key(start)
-    seen = {key0: []}
-    frontier = [key0]
-    while frontier:
-        nxt = []
-        for key in frontier:
-            for a in range(4):
-                e = O.EnvBatch(name, 1, seed=seed)
-                for pa in seen[key]:
-                    e.step(0, pa)
-                r, h, d, _ = e.step(0, a)
-                k2 = _key(e)
-                if not d and k2 not in seen and len(seen[key]) < 40:
-                    seen[k2] = seen[key] + [a]
-                    nxt.append(k2)
-        frontier = nxt
-    return seen
+    """BFS over the oracle: (agent_cell, box_cell, mode bit) triples reachable from reset, with an action path to each (the one
+    search the state sweeps use: tests/state_sweep.py)."""
+    return SS.reachable(name, seed, 0)
 
 
 def test_transition_tables_match_oracle_everywhere():
