@@ -839,6 +839,27 @@ SGK_API int sgk_members_vote(sgk_env *h, const uint8_t *member_actions_dev, int3
  * does). SGK_ERR_INVALID as sgk_members_vote, and for n_envs < 0. */
 SGK_API int sgk_members_vote_host(const uint8_t *member_actions, int32_t n_members, int64_t n_envs, const int32_t *member_ids,
                                   int32_t n_voters, const uint8_t *live, uint8_t *actions_out, uint16_t *votes_out, int64_t *dissent);
+/* The cross product for the CONVOLUTIONAL body: n_members conv bodies x all n_envs envs in one launch, what sgk_policy_act_members_all
+ * is for the MLP bodies; sgk_members_vote then votes over its actions as over the MLP's. Entry [m][e] of member_actions_dev is member
+ * m's GREEDY action on env e's current board: sgk_convq_act with epsilon = 0 and the m-th slice of the ten weight tensors, which are
+ * stacked on a leading member axis as for sgk_convq_rollout_members (`w` addresses member 0; for a PPOCNNAgent wh / bh = actor_cnn and
+ * wl / bl = actor_linear, so the action is PPOBaseAgent.act's argmax of the policy). The first maximum wins; no random number is drawn.
+ * member_scores_dev receives the four outputs behind every action. Actions and scores of member m are BIT-IDENTICAL to those of
+ * sgk_convq_act(epsilon 0) called with member m's slices: the member instantiation of the same kernel -- a workgroup serves one member
+ * for the whole launch, stages that member's weights once and walks the passes of envs; the grid is workgroups-per-member x n_members.
+ * The env state and the boards are read, never written; no allocation, no host synchronisation, legal inside a stream capture. Shapes:
+ * sgk_convq_act's. SGK_ERR_INVALID for a NULL `w` or weight pointer, another n_channels / n_layers, a NULL `out` or member_actions_dev,
+ * n_members outside 1 .. 4096, a member_scores_dev that is not 16-byte aligned (all checked before the handle is looked at), a NULL
+ * handle and a board shape without the kernel.
+ * The two outputs travel in a descriptor passed by const pointer, not as two pointer parameters: tests/test_guard_arena_cpu.py requires
+ * every non-const pointer PARAMETER of this header to be listed in the COVERED / EXEMPT tables of tests/test_gpu_guard_bands.py. Until
+ * sgk_members_act_out is listed there (STRUCTS and the tables), tests/test_gpu_convq_ensemble.py carries the guard-band cases of both
+ * fields and tests/test_convq_ensemble_abi.py requires every field of the struct to name one. */
+typedef struct sgk_members_act_out {
+  uint8_t *member_actions_dev; /* uint8 [n_members][n_envs], required */
+  float *member_scores_dev;    /* float32 [n_members][n_envs][4], 16-byte aligned, or NULL */
+} sgk_members_act_out;
+SGK_API int sgk_convq_act_members_all(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, const sgk_members_act_out *out);
 
 /* ---- PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186), batched ------------------------------ */
 /* rewards_dev / returns_dev: float32 [n_trajectories][t_max] row-major; lengths_dev: int32 [n_trajectories] or NULL

@@ -973,6 +973,24 @@ int sgk_convq_sample(sgk_env *h, const sgk_convq_weights *w, uint64_t draw_index
   return convq_launch(h, w, 1, 0.0, draw_index, nullptr, draw_index_dev, actions_out_dev, logits_out_dev);
 } SGK_CATCH_STATUS
 
+int sgk_convq_act_members_all(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, const sgk_members_act_out *out) try {
+  // (the arguments first: the refusals need no handle and no device)
+  if (int rc = convq_weights_ok(w)) return rc;
+  if (!out) return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: out is NULL");
+  if (!out->member_actions_dev) return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: member_actions_dev is NULL");
+  if (n_members < 1 || n_members > SGK_MEMBERS_MAX)
+    return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: n_members must be in 1..%d (got %d)", SGK_MEMBERS_MAX, (int)n_members);
+  if (out->member_scores_dev && ((uintptr_t)out->member_scores_dev & 15u))
+    return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: member_scores_dev must be 16-byte aligned");
+  SGK_CHECK_HANDLE(h);
+  if (!sgk::convq_board_has_kernel(h->sh.rules_host.height, h->sh.rules_host.width))
+    return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: the fused conv body does not cover %d x %d boards", h->sh.rules_host.height,
+                h->sh.rules_host.width);
+  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  SGK_HIP(sgk::launch_convq_act_members(h->sh, cw, w->n_channels, n_members, out->member_actions_dev, out->member_scores_dev, h->stream));
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_step_store(sgk_env *h, const uint8_t *actions_dev, uint32_t flags, int32_t cheat, int64_t slice, const int64_t *slice_dev,
                    int32_t ring_slices, int8_t *successors_ring, uint8_t *actions_ring, int8_t *rewards_ring, uint8_t *terminals_ring) try {
   SGK_CHECK_HANDLE(h);

@@ -1,4 +1,5 @@
-// sgk_convq.hip -- the reference's convolutional body, forward + draw for every env in ONE launch (sgk_convq_sample, sgk_convq_act).
+// sgk_convq.hip -- the reference's convolutional body, forward + draw for every env in ONE launch (sgk_convq_sample, sgk_convq_act; sgk_convq_act_members_all: n_members
+// stacked bodies x every env).
 //
 // The network is PPOCNNAgent's (policy_cnn.py:17-81) trunk and ONE four-way head:
 //     trunk = relu(conv3x3(relu(conv3x3(x, 1 -> C)), C -> C)) + conv1x1(x, 1 -> C)          (n_layers = 2, the reference's default)
@@ -43,7 +44,16 @@ namespace sgk {
 
 // (the ten weight tensors as restrict-qualified kernel arguments, not as a struct of pointers: only then may the per-channel constants
 // and the fifth channel's weights be read through the scalar cache inside the pass loop, next to the kernel's own stores)
-template <int HH, int WW, int C>
+//
+// MEMBERS = true (sgk_convq_act_members_all): the cross product, every member's greedy action on every env. The grid is (workgroups per
+// member, n_members): workgroup b = blockIdx.y * gridDim.x + blockIdx.x serves member b / gridDim.x = blockIdx.y for the whole launch --
+// the ten weight pointers address member 0 of tensors stacked [n_members][...] and are moved to the member's slices here (the strides of
+// convq_rollout_kernel<ENV, C, true>), so cq_setup stages that member's weights once; the outputs are [n_members][n](, [4]) and are moved
+// to the member's rows -- and its grid-stride loop over ALL n envs' passes runs along x, as in the shared kernel. The member's action is
+// greedy: select_action's first maximum with a draw that is never below epsilon 0, no Philox block; mode, eps, seed, env_base, draw and
+// the two device scalars are not read. Everything else is the same code, so member m's scores and actions are the bytes the
+// MEMBERS = false kernel leaves for member m's slices and epsilon 0.
+template <int HH, int WW, int C, bool MEMBERS = false>
 __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
     const int8_t *__restrict__ boards, int pitch, const float *__restrict__ w1r, const float *__restrict__ b1r, const float *__restrict__ w2r,
     const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr, const float *__restrict__ whr,
@@ -55,8 +65,17 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
   float *Lf = reinterpret_cast<float *>(convq_smem);
   float *WL = Lf + G::O_WL, *act = Lf + G::O_ACT;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (eps_ptr) eps = *eps_ptr;  // device-resident scalars: the launch can be replayed from a graph
-  if (draw_ptr) draw = *draw_ptr;
+  if constexpr (MEMBERS) {
+    const size_t m = blockIdx.y;  // this member's slice of the ten stacked tensors, its rows of the outputs
+    w1r += m * (C * G::K1); b1r += m * C; w2r += m * (C * G::K2); b2r += m * C; wbr += m * C; bbr += m * C; whr += m * (C * G::K2);
+    bhr += m * C;
+    wlr += m * (4 * G::NF); blr += m * 4;
+    actions += m * (size_t)n;
+    if (scores_out) scores_out += m * (size_t)n * 4;
+  } else {
+    if (eps_ptr) eps = *eps_ptr;  // device-resident scalars: the launch can be replayed from a graph
+    if (draw_ptr) draw = *draw_ptr;
+  }
   CqLane<G> L;
   cq_setup<G, WW, C>(L, WL, act, w1r, w2r, whr, wlr);
   // ---- this lane's board bytes of a pass ----
@@ -104,8 +123,12 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
         const int64_t env = env0 + (idx >> 2);
         if (idx < G::ENVS * 4 && (idx & 3) == 0 && env < n) {
           // mode 0: DeepQAgent.act_explore's epsilon-greedy draw on four scores; mode 1: Categorical(logits).sample() (PPOCNNAgent)
-          actions[env] = (uint8_t)(mode == 0 ? pick_action<0>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps)
-                                             : pick_action<1>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps));
+          if constexpr (MEMBERS) {
+            actions[env] = (uint8_t)select_action<0>(q0, q1, q2, q3, 1.0, 0u, 0.0);  // (u = 1 is never below epsilon 0: the first maximum)
+          } else {
+            actions[env] = (uint8_t)(mode == 0 ? pick_action<0>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps)
+                                               : pick_action<1>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps));
+          }
           if (scores_out) *reinterpret_cast<float4 *>(scores_out + 4 * env) = make_float4(q0, q1, q2, q3);
         }
       }
@@ -149,6 +172,52 @@ hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channe
 #undef SGK_CONVQ_LAUNCH_C
 #undef SGK_CONVQ_LAUNCH
   return hipGetLastError();
+}
+
+// the member instantiation: a member's workgroups are one per pass while all members' fit the chip (one member: the single kernel's
+// grid), at least one -- the members rollout's rule (launch_convq_rollout) with the single launcher's per_cu
+hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, uint8_t *member_actions,
+                                    float *member_scores, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n_members < 1 || n_members > SGK_MEMBERS_MAX) return hipErrorInvalidValue;
+  const int H = sh.rules_host.height, W = sh.rules_host.width;
+#define SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, CV)                                                                               \
+  do {                                                                                                                     \
+    constexpr size_t lds = ConvQGeom<HV, WV, CV>::lds_bytes;                                                               \
+    const int64_t n_pass = (sh.n + ConvQGeom<HV, WV, CV>::ENVS - 1) / ConvQGeom<HV, WV, CV>::ENVS;                         \
+    hipError_t ae = allow_dynamic_lds<convq_act_kernel<HV, WV, CV, true>>(sh.device, (int)lds);                            \
+    if (ae != hipSuccess) return ae;                                                                                       \
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                 \
+    const int member_wgs = grid_for(n_pass, std::max(sh.n_cus * per_cu / n_members, 1));                                   \
+    convq_act_kernel<HV, WV, CV, true><<<dim3(member_wgs, n_members), dim3(CQ_WG), lds, st>>>(                             \
+        sh.boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl, member_actions, member_scores, sh.n, 0, 0.0, 0, 0, 0, \
+        nullptr, nullptr);                                                                                                 \
+  } while (0)
+#define SGK_CONVQ_MEMBERS_LAUNCH_C(HV, WV)                                                                                 \
+  do {                                                                                                                     \
+    if (n_channels == 5) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 5);                                                              \
+    else if (n_channels == 4) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 4);                                                         \
+    else if (n_channels == 8) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 8);                                                         \
+    else return hipErrorInvalidValue;                                                                                      \
+  } while (0)
+  if (H == 5 && W == 5) SGK_CONVQ_MEMBERS_LAUNCH_C(5, 5);
+  else if (H == 6 && W == 5) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 5);
+  else if (H == 6 && W == 6) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 6);
+  else if (H == 6 && W == 8) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 8);
+  else if (H == 7 && W == 7) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 7);
+  else if (H == 7 && W == 8) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 8);
+  else if (H == 7 && W == 9) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 9);
+  else return hipErrorInvalidValue;
+#undef SGK_CONVQ_MEMBERS_LAUNCH_C
+#undef SGK_CONVQ_MEMBERS_LAUNCH
+  return hipGetLastError();
+}
+
+bool convq_board_has_kernel(int height, int width) {
+  const int boards[][2] = {{5, 5}, {6, 5}, {6, 6}, {6, 8}, {7, 7}, {7, 8}, {7, 9}};
+  for (const auto &b : boards)
+    if (b[0] == height && b[1] == width) return true;
+  return false;
 }
 
 }  // namespace sgk

@@ -109,6 +109,12 @@ struct ConvQWeights {
 // mode 0: epsilon-greedy on the four scores (DeepQAgent.act_explore); 1: Categorical(logits = scores).sample() (PPOBaseAgent.act_explore)
 hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, uint8_t *actions, float *scores, double eps, uint64_t draw,
                             const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
+// the cross product (sgk_convq_act_members_all; the member instantiation of the same kernel): `w` addresses member 0 of the ten weight
+// tensors stacked [n_members][...]; member m's greedy action on EVERY env -> member_actions [n_members][n], its four outputs ->
+// member_scores [n_members][n][4] or null
+hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, uint8_t *member_actions,
+                                    float *member_scores, hipStream_t st);
+bool convq_board_has_kernel(int height, int width);  // the board shapes launch_convq_act dispatches
 // n_steps of {conv forward, draw, env.step} in one launch (sgk_convq_rollout.hip); outputs as for launch_policy_rollout.
 // n_members >= 1 (sgk_convq_rollout_members; 0: sgk_convq_rollout's own kernel): `w` addresses member 0 of the ten weight tensors stacked
 // [n_members][...], member m acts in the envs m * n / n_members ..; member_metrics as for launch_policy_rollout

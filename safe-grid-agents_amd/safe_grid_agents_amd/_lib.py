@@ -111,6 +111,11 @@ class SgkMembersTensor(ctypes.Structure):
     _fields_ = [("base", ctypes.c_void_p), ("bytes_per_member", ctypes.c_uint64)]
 
 
+class SgkMembersActOut(ctypes.Structure):
+    """sgk_members_act_out: the two outputs of sgk_convq_act_members_all."""
+    _fields_ = [("member_actions_dev", ctypes.c_void_p), ("member_scores_dev", ctypes.c_void_p)]
+
+
 MEMBERS_MAX, MEMBERS_MAX_TENSORS, MEMBERS_MAX_COLUMNS, MEMBERS_BAD_SOURCE = 4096, 64, 8, 1
 PPO_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkPpoMemberHyper._fields_)
 DQN_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkDqnMemberHyper._fields_)
@@ -205,6 +210,7 @@ _SIGNATURES = {
     "sgk_policy_rollout_members_eps": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                                       ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V, _V]),
     "sgk_policy_act_members_all": (ctypes.c_int, [_V, ctypes.POINTER(SgkMlpWeights), ctypes.c_int32, _V, _V]),
+    "sgk_convq_act_members_all": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.POINTER(SgkMembersActOut)]),
     "sgk_members_vote": (ctypes.c_int, [_V, _V, ctypes.c_int32, _V, ctypes.c_int32, _V, _V, _V]),
     "sgk_members_vote_host": (ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
     "sgk_discounted_returns": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_double]),

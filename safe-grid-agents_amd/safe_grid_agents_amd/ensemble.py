@@ -6,16 +6,20 @@ population-based training; for deep-q it is the Q-ensemble's evaluation). One lo
 (include/sgk.h):
 
   sgk_policy_act_members_all   the cross product: member m's greedy action on env e's board for every (m, e), uint8 [M][N]; a workgroup
-                               serves one member for the whole launch and stages its weights once
+                               serves one member for the whole launch and stages its weights once (ppo-mlp, deep-q: the MLP kernel)
+  sgk_convq_act_members_all    the same cross product for the conv bodies (ppo-cnn): the member instantiation of the 4 x 4 x 1 MFMA
+                               conv kernel, member m's row the bytes sgk_convq_act(epsilon 0) leaves for its slices
   sgk_members_vote             one lane per env counts the voters' actions; the first action with the most votes wins (np.argmax's tie
                                rule); two int64 counters gain the dissent (voters that did not vote for the winner) and the votes cast
-                               over the envs whose episode is not over -- disagreement = dissent / votes, exact
+                               over the envs whose episode is not over -- disagreement = dissent / votes, exact; body-agnostic
 
 EnsembleMixin.ensemble_act() is one such step without the env's; evaluate_ensemble() is batched_default_eval's schedule with the ensemble
-as the agent. A population supplies _ensemble_weights(): its members' greedy MLP weights, stacked, at addresses that stay. Nothing
-here touches the members' weights, optimiser state, metrics, epsilon or draw counters: greedy acting draws nothing.
+as the agent. A population supplies _ensemble_weights(): its members' greedy weights, stacked, at addresses that stay -- and, when its
+forward is not the MLP kernel, _ensemble_act_all(): the acting launch (BatchedPPOCNNPopulation's is the conv one). Nothing here touches
+the members' weights, optimiser state, metrics, epsilon or draw counters: greedy acting draws nothing.
 
-This module also holds the command line's side: --ensemble-eval (check_ensemble_eval: SystemExit with a plain message).
+This module also holds the command line's side: --ensemble-eval (check_ensemble_eval: SystemExit with a plain message). The command line
+covers the MLP populations; the conv ensemble is reached through the Python API (BatchedPPOCNNPopulation.evaluate_ensemble).
 """
 from . import _lib
 from .metering import BatchMetrics
@@ -24,7 +28,8 @@ ENSEMBLE_AGENTS = ("ppo-mlp", "deep-q")  # the populations whose forward is the 
 
 
 class EnsembleMixin:
-    """ensemble_act() / evaluate_ensemble() for a population with `env`, `n_members`, `device` and an _ensemble_weights() method.
+    """ensemble_act() / evaluate_ensemble() for a population with `env`, `n_members`, `device` and an _ensemble_weights() method (and,
+    for a body that is not the MLP, its own _ensemble_act_all()).
 
     The buffers are made once per population and reused by every call and every recorded graph: member_actions uint8 [M, N], actions
     uint8 [N], ids int32 [M] (a selection's member indices in its first entries), dissent int64 [2]."""
@@ -33,6 +38,11 @@ class EnsembleMixin:
 
     def _ensemble_weights(self):
         raise NotImplementedError
+
+    def _ensemble_act_all(self, weights, out):
+        """The acting launch: every member's greedy action on every env, `weights` = _ensemble_weights(), into out uint8 [M, N]. The
+        default is the MLP bodies' kernel; a population with another forward overrides it."""
+        self.env.policy_act_members_all(weights, self.n_members, out=out)
 
     def _ensemble_state(self):
         import torch
@@ -82,12 +92,12 @@ class EnsembleMixin:
         st = self._ensemble_state()
         ids = self._ensemble_members(members)
         env = self.env
-        env.policy_act_members_all(self._ensemble_weights(), self.n_members, out=st["member_actions"])
+        self._ensemble_act_all(self._ensemble_weights(), st["member_actions"])
         return env.members_vote(st["member_actions"], members=ids, out=out, votes_out=votes_out)
 
     def _ensemble_step(self, weights, ids, reset_done):
         st, env = self._ens, self.env
-        env.policy_act_members_all(weights, self.n_members, out=st["member_actions"])
+        self._ensemble_act_all(weights, st["member_actions"])
         env.members_vote(st["member_actions"], members=ids, out=st["actions"], dissent=st["dissent"])
         env.step(st["actions"], auto_reset=False)
         if reset_done:
@@ -118,7 +128,7 @@ class EnsembleMixin:
             graphs = st["graphs"].get(key)
             if graphs is None:
                 # (eager once, without the env's step: the kernels' first-launch set-up does not belong in a recording)
-                env.policy_act_members_all(weights, self.n_members, out=st["member_actions"])
+                self._ensemble_act_all(weights, st["member_actions"])
                 env.members_vote(st["member_actions"], members=ids, out=st["actions"])
                 torch.cuda.synchronize(env.device)
                 graphs = []
@@ -146,7 +156,7 @@ class EnsembleMixin:
 # -- the command line ---------------------------------------------------------------------------------------------------------------
 def check_ensemble_eval(args):
     """--ensemble-eval of `args` -> True / False. SystemExit with a plain message without --members and for an agent whose population
-    has no ensemble (ppo-cnn: its forward is another kernel)."""
+    is not in ENSEMBLE_AGENTS (ppo-cnn: its ensemble is a Python-API feature, BatchedPPOCNNPopulation.evaluate_ensemble)."""
     if not getattr(args, "ensemble_eval", False):
         return False
     if args.agent_alias not in ENSEMBLE_AGENTS:

@@ -1028,6 +1028,29 @@ class BatchedGridworldEnv:
             (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
         self._sync_lib_to_torch()
 
+    def convq_act_members_all(self, weights, n_members, n_channels, n_layers=2, out=None, scores_out=None):
+        """Every member's GREEDY action on EVERY env's current board in ONE HIP launch (sgk_convq_act_members_all): the conv bodies'
+        cross product, what policy_act_members_all is for the MLP bodies. `weights` stacked on a leading member axis (see
+        _member_convq_weights; wh / bh / wl / bl = the actor head); returns uint8 [n_members, N] (`out` when given), row m what
+        convq_act(member m's slices, epsilon=0.0) gives, bit for bit; scores_out: float32 [n_members, N, 4] on this device that
+        receives the four outputs, or None. The envs are not touched."""
+        import torch
+
+        n_members = int(n_members)
+        if not 1 <= n_members <= _lib.MEMBERS_MAX:
+            raise ValueError("n_members must be in 1..%d, not %d" % (_lib.MEMBERS_MAX, n_members))
+        w = self._member_convq_weights(weights, n_members, n_channels, n_layers)
+        if out is None:
+            out = torch.empty((n_members, self.n_envs), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._check(out, "out", shape=(n_members, self.n_envs), dtypes=("uint8",))
+        sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(n_members, self.n_envs, 4),
+                                                                         dtypes=("float32",)).data_ptr())
+        o = _lib.SgkMembersActOut(ctypes.c_void_p(out.data_ptr()), sp)
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_convq_act_members_all(self._h.ptr, ctypes.byref(w), n_members, ctypes.byref(o)))
+        self._sync_lib_to_torch()
+        return out
+
     def ppo_cnn_members_workspace_bytes(self, n_channels, batch, n_members):
         """Bytes of device workspace sgk_ppo_cnn_epochs_members needs on this level for n_members members with n_channels and batch
         rows; SgkError when unsupported."""

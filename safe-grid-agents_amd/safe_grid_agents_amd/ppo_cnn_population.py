@@ -13,6 +13,9 @@ What member m computes is what a BatchedPPOAgent(body="cnn", fused_conv_learn=Tr
 env_index_base + m * E with the handle's seed, member m's weights, member_keys[m] as the key of its minibatch draws and member m's
 hyper-parameters in its `args` -- bit for bit (tests/test_gpu_ppo_cnn_members.py, tests/test_gpu_member_hyper.py), and through that the reference's own run (tests/golden/batched_ppo_cnn_*.npz).
 
+The members can also act as ONE agent on all N envs (ensemble.EnsembleMixin: ensemble_act(), evaluate_ensemble()): every member's greedy
+action on every board in one launch (sgk_convq_act_members_all), then the plurality vote (sgk_members_vote).
+
 There is no torch path for a population: a shape without a kernel is a ValueError in the constructor.
 """
 import ctypes
@@ -21,6 +24,7 @@ import types
 import torch
 
 from . import _lib
+from .ensemble import EnsembleMixin
 from .metering import BatchMetrics
 from .ppo import BatchedPPOAgent, PPOCNNAgent
 from .ppo_population import _INT64_MIN, _MASK, PPOMemberHyper, _as_i64, default_member_seed
@@ -53,8 +57,9 @@ def unstack_state_dict(stacked, m):
     return {key: stacked[name][m].detach().clone() for key, name in zip(MEMBER_KEYS, PARAMS)}
 
 
-class BatchedPPOCNNPopulation(PPOMemberHyper):
-    """M independent PPOCNNAgents over env's N = M x E envs (see the module docstring).
+class BatchedPPOCNNPopulation(EnsembleMixin, PPOMemberHyper):
+    """M independent PPOCNNAgents over env's N = M x E envs (see the module docstring). ensemble_act() / evaluate_ensemble()
+    (ensemble.EnsembleMixin) let the M members act as one agent on all N envs: every member votes on every env.
 
     args: the ppo-cnn flags (lr, discount, batch_size, epochs, clipping, entropy_bonus, critic_coeff, n_layers, n_channels, seed).
     member_seeds: member m's initial weights are those of PPOCNNAgent(env, args) built under torch.manual_seed(member_seeds[m])
@@ -185,6 +190,14 @@ class BatchedPPOCNNPopulation(PPOMemberHyper):
         """The rollout kernel's ten tensors (trunk, bottleneck, actor_cnn as the head, actor_linear) out of stacked tensors."""
         return {"w1": t["w1"], "b1": t["b1"], "w2": t["w2"], "b2": t["b2"], "wb": t["wb"], "bb": t["bb"], "wh": t["wa"], "bh": t["ba"],
                 "wl": t["la"], "bl": t["lab"]}
+
+    def _ensemble_weights(self):
+        """EnsembleMixin: the tensors evaluate() acts greedily with -- the population's own, their addresses stay."""
+        return self._acting_weights(self.cur)
+
+    def _ensemble_act_all(self, weights, out):
+        """EnsembleMixin's acting launch for the conv bodies: sgk_convq_act_members_all."""
+        self.env.convq_act_members_all(weights, self.n_members, self.n_channels, out=out)
 
     def gather_rollout(self, cheat=False, horizon=None):
         """PPOBaseAgent.gather_rollout (reference policy_base.py:133-177) of every member at once: one episode per env under its
