@@ -311,7 +311,12 @@ SGK_API int sgk_tabq_create(sgk_env *env, double lr, double discount, double eps
  * board shows), `hash_capacity` slots per agent (a power of two, 64 .. 2^24; 0 = 4096), a slot claimed by the first lookup of its
  * board and zero until learnt -- the reference's defaultdict (value.py:31-36). 36 bytes per slot and agent. hash_capacity must be 0
  * for every other level. A board that finds its agent's table full gets no row: it reads zeros (what a fresh defaultdict row
- * holds), learns nothing, and raises a flag (sgk_tabq_hash_info) -- re-create the agents with more slots. */
+ * holds), learns nothing, and raises a flag (sgk_tabq_hash_info) -- re-create the agents with more slots. Around an episode
+ * boundary the fused calls (sgk_tabq_step, sgk_tabq_learn_steps without SGK_F_SEPARATE_LAUNCHES, sgk_tabq_rollout) look the next
+ * episode's start board up in the step that ENDS the episode, behind s', where the per-step calls do at the next sgk_tabq_act: no
+ * lookup lies between the two moments, so the order in which boards claim slots is the same and the tables differ -- by that one
+ * slot, a row of zeros, or by the flag where the table was full -- only while a run stands exactly on the boundary and the start
+ * board is new to the agent (agents created after their envs have moved). */
 SGK_API int sgk_tabq_create_ex(sgk_env *env, double lr, double discount, double epsilon, int64_t epsilon_anneal,
                                int32_t hash_capacity, sgk_tabq **out);
 /* capacity (0: perfect-hash level), slots in use in the fullest agent's table (counted by a kernel: a diagnostic), and whether

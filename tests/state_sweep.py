@@ -22,7 +22,8 @@ COIN_ENVS = ("AbsentSupervisor-v0", "SafeInterruptibility-v0")
 SWEPT = ("BoatRace-v0", "IslandNavigation-v0", "SideEffectsSokoban-v0", "DistributionalShift-v0", "AbsentSupervisor-v0",
          "SafeInterruptibility-v0", "ConveyorBelt-v0")
 # WhiskyGold replaces actions by its own draws once the whisky is drunk, TomatoWatering and FriendFoe draw every step: the same
-# machinery with scripts built on env index 0, no coverage requirement (what they reach is logged)
+# machinery with scripts built on env index 0, no coverage requirement (what they reach is logged). TomatoWatering's requirement is
+# stated in events and planned per env around its drying schedule: tests/tomato_sweep.py
 UNSWEPT = ("WhiskyGold-v0", "TomatoWatering-v0", "FriendFoe-v0")
 DEPTH_CAP = 98  # the episode limit is 100 steps; the deepest state (ConveyorBelt) is found at depth 19
 SEED = 5
