@@ -311,7 +311,8 @@ SGK_API int sgk_tabq_create(sgk_env *env, double lr, double discount, double eps
  * board shows), `hash_capacity` slots per agent (a power of two, 64 .. 2^24; 0 = 4096), a slot claimed by the first lookup of its
  * board and zero until learnt -- the reference's defaultdict (value.py:31-36). 36 bytes per slot and agent. hash_capacity must be 0
  * for every other level. A board that finds its agent's table full gets no row: it reads zeros (what a fresh defaultdict row
- * holds), learns nothing, and raises a flag (sgk_tabq_hash_info) -- re-create the agents with more slots. Around an episode
+ * holds), learns nothing, and raises a flag (sgk_tabq_hash_info) -- re-create the agents with more slots, or grow the tables before they fill
+ * (sgk_tabq_hash_grow). Around an episode
  * boundary the fused calls (sgk_tabq_step, sgk_tabq_learn_steps without SGK_F_SEPARATE_LAUNCHES, sgk_tabq_rollout) look the next
  * episode's start board up in the step that ENDS the episode, behind s', where the per-step calls do at the next sgk_tabq_act: no
  * lookup lies between the two moments, so the order in which boards claim slots is the same and the tables differ -- by that one
@@ -322,6 +323,24 @@ SGK_API int sgk_tabq_create_ex(sgk_env *env, double lr, double discount, double 
 /* capacity (0: perfect-hash level), slots in use in the fullest agent's table (counted by a kernel: a diagnostic), and whether
  * any board found its table full. Synchronises. Any output may be NULL; with max_used_out NULL the call is a 4-byte copy. */
 SGK_API int sgk_tabq_hash_info(sgk_tabq *q, int32_t *capacity_out, int32_t *max_used_out, int32_t *overflowed_out);
+/* Hashed levels: every agent's table rehashed on the device into one of `new_capacity` slots (a power of two in 64 .. 2^24, not
+ * below the current capacity; one capacity serves all agents), rows intact, in the middle of a run: every board keeps its row,
+ * bit for bit, in the slot its probe sequence gives it at the new capacity (old slots are moved in ascending order, so two growths
+ * of equal tables leave equal bytes), unclaimed slots are empty with zero rows, and an sgk_tabq_act made before the growth is still
+ * learnt from after it. Grown ahead of need (capacity >= slots in use + 2 per lockstep step to come: a step looks up at most two
+ * boards new to an agent) no board is ever refused and a run equals the reference's unbounded dictionary whatever capacity it
+ * started with. An equal capacity is a no-op. SGK_ERR_INVALID with nothing launched or changed: a NULL handle, a perfect-hash
+ * level, a capacity that is no power of two in range or below the current one. A failed allocation is SGK_ERR_HIP and leaves the
+ * agents as they were, still usable (both tables exist side by side for the length of the call: 36 bytes x (old + new) slots per
+ * agent).
+ *  - The call ALLOCATES and SYNCHRONISES (it waits for the handle's stream, frees the old arrays and drops the hipGraphs that
+ *    sgk_tabq_learn_steps recorded, which carry the old pointers): it cannot be captured in a hipGraph.
+ *  - A pointer obtained earlier from sgk_tabq_table_dev is DEAD after a growth: ask again.
+ *  - The overflow flag is sticky: growth does not clear it.
+ *  - The per-step sgk_tabq_learn skips an agent whose pending sgk_tabq_act was REFUSED (its table was full), the look-up of s'
+ *    included. A growth between such a refused act and its learn leaves that one step unlearnt and s' unclaimed, where a dictionary
+ *    would admit both boards then. Growing between whole steps, or before any refusal, has no such case. */
+SGK_API int sgk_tabq_hash_grow(sgk_tabq *q, int32_t new_capacity);
 /* hashed levels: uint32 [env_count][hash_capacity], the board each slot holds (0xffffffff = empty; tomato watering: agent cell |
  * shown watered set << 8, 0x2000 = the bucket's delusion board), row-aligned with sgk_tabq_copy_table's [env][slot][action] */
 SGK_API int sgk_tabq_copy_keys(sgk_tabq *q, int64_t env_begin, int64_t env_count, uint32_t *keys_host);

@@ -1625,6 +1625,48 @@ int sgk_tabq_copy_keys(sgk_tabq *q, int64_t env_begin, int64_t env_count, uint32
   return SGK_OK;
 } SGK_CATCH_STATUS
 
+int sgk_tabq_hash_grow(sgk_tabq *q, int32_t new_capacity) try {
+  if (!q) return fail(SGK_ERR_INVALID, "handle is NULL");
+  sgk_env *h = q->env;
+  SGK_CHECK_HANDLE(h);
+  if (!q->tq.hash_cap) return fail(SGK_ERR_INVALID, "this level's tables are indexed by a perfect hash: there is no hash table to grow");
+  if (new_capacity < 64 || new_capacity > (1 << 24) || (new_capacity & (new_capacity - 1)))
+    return fail(SGK_ERR_INVALID, "new_capacity must be a power of two in 64 .. 2^24 (slots per agent)");
+  if (new_capacity < q->tq.hash_cap)
+    return fail(SGK_ERR_INVALID, "new_capacity %d is below the current %d: hash tables do not shrink", (int)new_capacity, (int)q->tq.hash_cap);
+  if (new_capacity == q->tq.hash_cap) return SGK_OK;
+  const size_t n = (size_t)h->sh.n;
+  const size_t kbytes = sizeof(uint32_t) * n * (size_t)new_capacity, tbytes = sizeof(double) * n * (size_t)new_capacity * SGK_ACTIONS;
+  uint32_t *keys_new = nullptr;
+  double *table_new = nullptr;
+  hipError_t e = hipMalloc(&keys_new, kbytes);
+  if (e == hipSuccess) e = hipMalloc(&table_new, tbytes);
+  if (e == hipSuccess) e = hipMemsetAsync(keys_new, 0xff, kbytes, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(table_new, 0, tbytes, h->stream);  // defaultdict(zeros) (value.py:31)
+  if (e == hipSuccess) e = sgk::launch_tabq_hash_grow(h->sh, q->tq, keys_new, table_new, new_capacity, h->stream);
+  // (waited for even after a failure: a memset that did go out must not run into the hipFree below)
+  const hipError_t we = sgk::host::wait_stream(h->stream);
+  if (e == hipSuccess) e = we;
+  if (e != hipSuccess) {  // the agent is as it was: the old arrays are still the tables
+    (void)hipGetLastError();
+    (void)hipFree(keys_new);
+    (void)hipFree(table_new);
+    return hip_fail(e, "growing the tabular-Q hash tables");
+  }
+  (void)hipFree(q->tq.keys);
+  (void)hipFree(q->tq.table);
+  q->tq.keys = keys_new;
+  q->tq.table = table_new;
+  q->tq.hash_cap = new_capacity;
+  q->tq.n_states = new_capacity;
+  if (q->copy_stage) {  // sized by the capacity: sgk_tabq_copy_table makes it again at its next call
+    (void)hipHostFree(q->copy_stage);
+    q->copy_stage = nullptr;
+  }
+  q->graphs.clear();  // the recorded launches carry the old pointers and the old n_states: a replay would write freed memory
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 // the per-step kernels' row slots (sgk_tabq.hip) mirror table rows: after anything else wrote the table they are re-tagged invalid
 static hipError_t refresh_row_tags(sgk_tabq *q) {
   if (!q->rows_stale) return hipSuccess;

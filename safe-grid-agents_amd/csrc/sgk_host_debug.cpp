@@ -5,6 +5,7 @@
 // (tests/test_switch_variants.py). Never used by a product path.
 #include <cstring>
 
+#include "sgk_tabq_hash.h"
 #include "sgk_transition.h"
 
 namespace sgk {
@@ -144,6 +145,36 @@ SGK_HOST_API int sgk_debug_level(int env_id, int32_t dims[4], uint8_t templ[64],
 }
 SGK_HOST_API int sgk_debug_rules(int env_id, SgkRules *out) { return (out && sgk_build_rules(env_id, out) == 0) ? SGK_OK : SGK_ERR_INVALID; }
 SGK_HOST_API int sgk_debug_rules_size(void) { return (int)sizeof(SgkRules); }
+// The hashed tabular-Q tables (sgk_tabq_hash.h) on the host, on the agent-major arrays sgk_tabq_copy_keys / sgk_tabq_copy_table hand
+// out: keys uint32 [n][cap], table float64 [n][cap][4]. Host-only library: not part of include/sgk.h.
+// One lookup of `key` in one agent's key row: the slot (claimed on a miss), or -1 with *overflow = 1 when the row is full.
+SGK_HOST_API int sgk_debug_tabq_hash_slot(uint32_t *keys, int32_t cap, uint32_t key, int32_t *overflow) {
+  if (!keys || !overflow || cap < 1 || (cap & (cap - 1))) return SGK_ERR_INVALID - 1;  // (-1 is an answer of the lookup itself)
+  return sgk::hash_slot(keys, cap, key, overflow);
+}
+// sgk_tabq_hash_grow's rehash for n agents, the kernel's loop (tabq_rehash_agent) agent by agent: keys_new / table_new are made
+// empty / zero here; tags (uint64 [n], may be NULL) follow as on the device. An equal capacity is what it is for sgk_tabq_hash_grow:
+// nothing moves (the outputs are copies).
+SGK_HOST_API int sgk_debug_tabq_rehash(const uint32_t *keys_old, const double *table_old, int64_t n, int32_t cap_old, int32_t cap_new,
+                                       uint32_t *keys_new, double *table_new, uint64_t *tags, int32_t *overflow) {
+  if (!keys_old || !table_old || !keys_new || !table_new || !overflow || n < 0) return SGK_ERR_INVALID;
+  if (cap_old < 4 || (cap_old & (cap_old - 1)) || cap_new < cap_old || (cap_new & (cap_new - 1))) return SGK_ERR_INVALID;
+  if (cap_new == cap_old) {
+    std::memcpy(keys_new, keys_old, sizeof(uint32_t) * (size_t)n * (size_t)cap_new);
+    std::memcpy(table_new, table_old, sizeof(double) * (size_t)n * (size_t)cap_new * SGK_ACTIONS);
+    return SGK_OK;
+  }
+  std::memset(keys_new, 0xff, sizeof(uint32_t) * (size_t)n * (size_t)cap_new);
+  std::memset(table_new, 0, sizeof(double) * (size_t)n * (size_t)cap_new * SGK_ACTIONS);
+  for (int64_t e = 0; e < n; ++e) {
+    const uint32_t *ko = keys_old + e * cap_old;
+    uint32_t *kn = keys_new + e * cap_new;
+    sgk::tabq_rehash_agent(ko, cap_old, kn, cap_new, table_old + e * cap_old * SGK_ACTIONS, SGK_ACTIONS,
+                           table_new + e * cap_new * SGK_ACTIONS, SGK_ACTIONS, overflow);
+    if (tags) tags[e] = sgk::tabq_rehash_tag(tags[e], ko, cap_old, kn, cap_new, overflow);
+  }
+  return SGK_OK;
+}
 SGK_HOST_API int sgk_random_action(uint64_t seed, uint64_t env_index, uint64_t t) { return sgk::host_random_action(seed, env_index, t); }
 SGK_HOST_API int sgk_debug_episode_coin(int env_id, uint64_t seed, uint64_t env_index, int n_resets) {
   SgkRules R;

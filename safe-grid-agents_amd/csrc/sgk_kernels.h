@@ -235,6 +235,10 @@ hipError_t launch_finished(const Shard &sh, int32_t *ids, int32_t *ret, int32_t 
 hipError_t launch_tabq_act(const Shard &sh, const TabqShard &tq, int explore, uint8_t *actions_out, hipStream_t st);
 hipError_t launch_tabq_forget_rows(const Shard &sh, const TabqShard &tq, hipStream_t st);
 hipError_t launch_tabq_hash_used(const Shard &sh, const TabqShard &tq, int32_t *max_used_dev, hipStream_t st);
+// sgk_tabq_grow.hip: tq's tables rehashed into keys_new (all 0xff) / table_new (all zero) of cap_new >= tq.hash_cap slots per agent;
+// tq.tags follow. tq itself is the caller's to swap afterwards.
+hipError_t launch_tabq_hash_grow(const Shard &sh, const TabqShard &tq, uint32_t *keys_new, double *table_new, int32_t cap_new,
+                                 hipStream_t st);
 hipError_t launch_tabq_learn(const Shard &sh, const TabqShard &tq, const uint8_t *actions, int cheat, hipStream_t st);
 // one lockstep step of tabq_learn in one launch (act_explore, env.step, learn, reset of the finished envs); actions_out may be null
 hipError_t launch_tabq_step(const Shard &sh, const TabqShard &tq, int cheat, uint32_t flags, uint8_t *actions_out, hipStream_t st);

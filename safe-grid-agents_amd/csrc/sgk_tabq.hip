@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "sgk_device.h"
+#include "sgk_tabq_hash.h"
 
 namespace sgk {
 
@@ -107,38 +108,16 @@ struct TabqArgs {
 // 1-4 kept table[agent][state][4]: every row access of a wave was 64 separate lines.)
 __device__ __forceinline__ int64_t row_of(const int64_t n, int si, int64_t env) { return ((int64_t)si * n + env) * 4; }
 
-// Tomato watering: the board (the reference's dictionary key) shows the agent's cell and which tomatoes are watered -- or, while
-// the agent stands on the bucket, the delusion board (every cell watered), whatever the true set is. key = cell | shown set << 8
-// (the tomato under the agent is hidden by it: its bit is cleared),
-// 0x2000 standing for the delusion. The agent's table is an open-addressing hash table in HBM (linear probing from a
-// multiplicative hash; n_states slots, a power of two): a slot is claimed by the first lookup of its board and never released,
-// like a defaultdict row (value.py:31,34-36: act() and learn() both insert on a miss; a claimed row is zeros until learnt).
-// One lane owns one agent, so nothing races inside a table.
-__device__ __forceinline__ int hash_slot(uint32_t *__restrict__ keys, int cap, uint32_t key, int32_t *overflow) {
-  int i = (int)((key * 0x9E3779B1u) >> 8) & (cap - 1);
-  for (int probes = 0; probes < cap; ++probes) {
-    const uint32_t k = keys[i];
-    if (k == key) return i;
-    if (k == 0xffffffffu) {
-      keys[i] = key;
-      return i;
-    }
-    i = (i + 1) & (cap - 1);
-  }
-  // Table full and the board is not in it: the flag is raised (sgk_tabq_hash_info; the trainer reads it at every period's sync
-  // point and stops) and the lookup answers "no row" (-1): the callers read zeros for it -- what a fresh defaultdict row holds --
-  // and skip the update, so no other board's row is touched.
-  *overflow = 1;
-  return -1;
-}
-
+// Tomato watering: the agent's table is an open-addressing hash table in HBM keyed by the board -- the key formula, the empty
+// marker and the probe loop (hash_slot) live in sgk_tabq_hash.h, shared with the growth kernel (sgk_tabq_grow.hip) and the host
+// restatement. One lane owns one agent, so nothing races inside a table.
 template <int ENV>
 __device__ __forceinline__ int state_index(const SgkRules &R, const EnvState &s, const TabqArgs &a, int64_t env) {
   if (ENV == SGK_TOMATO_WATERING) {
     // (the agent is drawn OVER the tomato it stands on: whether that one is watered does not show, so its bit is not part of the key)
     const uint32_t under = R.tomato_index[s.pos] != 255 ? (1u << R.tomato_index[s.pos]) : 0u;
-    const uint32_t shown = alt_backdrop<ENV>(R, s) ? 0x2000u : (((uint32_t)s.box | ((uint32_t)s.ext << 8)) & ~under);
-    return hash_slot(a.keys + env * a.n_states, a.n_states, (uint32_t)s.pos | (shown << 8), a.hash_overflow);
+    const uint32_t shown = alt_backdrop<ENV>(R, s) ? TABQ_HASH_DELUSION : (((uint32_t)s.box | ((uint32_t)s.ext << 8)) & ~under);
+    return hash_slot(a.keys + env * a.n_states, a.n_states, tabq_hash_key((uint32_t)s.pos, shown), a.hash_overflow);
   }
   return perfect_state_index<ENV>(R, s);
 }
@@ -1087,7 +1066,7 @@ __global__ __launch_bounds__(WG) void tabq_eval_hbm_kernel(TabqArgs a, int64_t n
 __global__ __launch_bounds__(WG) void tabq_hash_used_kernel(const uint32_t *__restrict__ keys, int64_t n, int cap, int32_t *__restrict__ max_used) {
   for (int64_t env = (int64_t)blockIdx.x * WG + threadIdx.x; env < n; env += (int64_t)gridDim.x * WG) {
     int used = 0;
-    for (int k = 0; k < cap; ++k) used += keys[env * cap + k] != 0xffffffffu;
+    for (int k = 0; k < cap; ++k) used += keys[env * cap + k] != TABQ_HASH_EMPTY;
     atomicMax(max_used, used);
   }
 }

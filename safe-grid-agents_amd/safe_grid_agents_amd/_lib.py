@@ -240,6 +240,7 @@ _SIGNATURES = {
                                           ctypes.POINTER(_V)]),
     "sgk_tabq_hash_info": (ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(ctypes.c_int32)]),
+    "sgk_tabq_hash_grow": (ctypes.c_int, [_V, ctypes.c_int32]),
     "sgk_tabq_copy_keys": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int64, _V]),
     "sgk_tabq_destroy": (ctypes.c_int, [_V]),
     "sgk_tabq_act": (ctypes.c_int, [_V, ctypes.c_int, _V]),

@@ -408,6 +408,33 @@ class BatchedTabularQAgent(ConsensusMixin, BaseActor, BaseLearner, BaseExplorer)
         _lib.check(self.lib.sgk_tabq_hash_info(self._h, ctypes.byref(c), ctypes.byref(u), ctypes.byref(o)))
         return c.value, u.value, bool(o.value)
 
+    HASH_CAPACITY_MAX = 1 << 24
+
+    def grow_hash(self, capacity):
+        """Hashed levels (TomatoWatering): every agent's table rehashed on the device into one of `capacity` slots (a power of two,
+        not below the current capacity), rows intact (sgk_tabq_hash_grow). Synchronises and allocates; a view obtained from table()
+        before the call is dead after it. Returns the capacity in force."""
+        self.env._follow()
+        _lib.check(self.lib.sgk_tabq_hash_grow(self._h, int(capacity)))
+        self.n_states = self.hash_capacity = int(capacity)  # (accepted: a power of two, the capacity from now on)
+        return self.hash_capacity
+
+    def reserve_hash(self, n_steps):
+        """Room for `n_steps` more lockstep steps in every agent's table: a step looks up at most two boards that are new to an
+        agent (s', and on `done` the next episode's start board), so with capacity >= used_max + 2 * n_steps + 1 no board is
+        refused in them. Grows (grow_hash) to the next power of two that satisfies the bound when the capacity is below it; returns
+        the capacity in force. Reads hash_info(): synchronises."""
+        cap, used, _ = self.hash_info()
+        if not cap:
+            raise RuntimeError("%s has a perfect hash of its boards: there is no hash table to reserve room in" % self.env.name)
+        need = used + 2 * int(n_steps) + 1
+        if cap >= need:
+            return cap
+        if need > self.HASH_CAPACITY_MAX:
+            raise RuntimeError("%d more steps need %d slots per agent (%d in use + 2 per step + 1), above the largest hash table "
+                               "of 2^24 slots" % (n_steps, need, used))
+        return self.grow_hash(1 << (need - 1).bit_length())
+
     def check_hash_overflow(self):
         """The cheap form of check_hash_tables (a 4-byte copy, no slot count): raise when some board found its agent's table full.
         The batched trainer calls it at every period's synchronisation point."""

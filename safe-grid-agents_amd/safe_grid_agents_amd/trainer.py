@@ -89,10 +89,15 @@ _PBT = [("pbt-every", "PE", dict(type=int, default=argparse.SUPPRESS)),
 _ENSEMBLE = ("ensemble-eval", "EN", dict(action="store_true", default=argparse.SUPPRESS))
 # --consensus-eval likewise (with another agent than tabular-q it parses and stops the run with a message: consensus.check_consensus_eval)
 _CONSENSUS = ("consensus-eval", "CE", dict(action="store_true", default=argparse.SUPPRESS))
+# extension, batched trainer (-N) on tomato only: `--hash-grow` grows the agents' hash tables on the device ahead of need
+# (BatchedTabularQAgent.reserve_hash before every training period and every evaluation), so that no board is ever refused and the run
+# equals the reference's unbounded dictionary whatever capacity it started with. Absent unless given; another level stops the run with a
+# message (check_hash_grow)
+_HASH_GROW = ("hash-grow", "HG", dict(action="store_true", default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
-    "tabular-q": [_LR, _EPS, _ANNEAL, _CONSENSUS],
+    "tabular-q": [_LR, _EPS, _ANNEAL, _CONSENSUS, _HASH_GROW],
     "deep-q": [_LR, _EPS, _ANNEAL,
                ("replay-capacity", "r", dict(type=int, default=10000)),
                ("sync-every", "s", dict(type=int, default=10000)),
@@ -225,6 +230,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         sweep = None  # the grid only gave the starting values: after a PBT step member m is no longer "point m % G"
     ensemble = {} if check_ensemble_eval(args) else None  # --ensemble-eval: the last ensemble evaluation's figures; SystemExit if it cannot run
     consensus = {} if check_consensus_eval(args) else None  # --consensus-eval likewise
+    hash_grow = check_hash_grow(args)  # --hash-grow: True / False; SystemExit on a level whose tables are not hashed
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if consensus is not None and world > 1:
@@ -309,6 +315,8 @@ def train_batched(args, writer_factory=None, reporter=_noop):
                 for _ in range(horizon):  # dqn_learn for every env: act_explore, step, replay add, one SGD step, epsilon, sync
                     agent.step(learn=True, cheat=args.cheat)
             else:
+                if hash_grow:  # room for this period's boards before they are looked up (each rank on its own fullest table)
+                    agent.reserve_hash(horizon)
                 agent.rollout(horizon, cheat=args.cheat)
                 if hasattr(agent, "check_hash_overflow"):
                     agent.check_hash_overflow()  # hashed tables (tomato watering): a full table stops the run at THIS period
@@ -369,6 +377,19 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     return agent, env
 
 
+def check_hash_grow(args):
+    """--hash-grow of `args` -> True / False. SystemExit with a plain message for an agent other than tabular-q and for a level other
+    than tomato: only its agents keep hash tables."""
+    if not getattr(args, "hash_grow", False):
+        return False
+    if args.agent_alias != "tabular-q":
+        raise SystemExit("--hash-grow grows the hash tables of tabular-q agents, not %r" % (args.agent_alias,))
+    if args.env_alias != "tomato":
+        raise SystemExit("--hash-grow runs on tomato only: %s has a perfect hash of its boards, its tables have no capacity to grow"
+                         % (args.env_alias,))
+    return True
+
+
 def sweep_grid(args):
     """--sweep NAME=v1,v2,... flags of `args` -> (names, grid) (member_hyper.parse_sweep; SystemExit with the valid names for a sweep
     that cannot run), or None without the flag."""
@@ -409,6 +430,8 @@ def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None, 
         print("#### EVAL ####")
     if hasattr(agent, "check_hash_tables"):
         agent.check_hash_tables()  # levels without a perfect hash of their boards: a full table is an error, not a silent state
+    if getattr(args, "hash_grow", False) and args.agent_alias == "tabular-q":  # greedy act() claims slots too
+        agent.reserve_hash(max(int(args.eval_timesteps) - 1, 0) + int(env.info.max_iterations))
     if hasattr(agent, "member_metrics"):  # a population: the two greedy phases through the members rollout
         agent.evaluate(args.eval_timesteps)
     else:
