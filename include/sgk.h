@@ -905,6 +905,89 @@ SGK_API int sgk_discount_powers(double discount, int32_t t_max, float *out_host)
 SGK_API int sgk_discounted_returns_members(sgk_env *h, const float *rewards_dev, const int32_t *lengths_dev, float *returns_dev,
                                            int64_t n_trajectories, int32_t t_max, int32_t n_members, const float *gamma_pow_dev);
 
+/* ---- PPOCRMDPAgent (reference spiky/agents.py:74-270): corrupt-reward detection and reward bounds ------------------------------
+ * What the agent does between a rollout and get_discounted_returns, on INTEGER keys and INTEGER rewards.
+ *
+ * Key. A successor observation of the transition env is (board before the step, board after it); on BoatRace a board is determined by
+ * the agent's cell, so key = prev_cell * n_cells + cur_cell (cells row-major), n_keys = n_cells^2 <= SGK_CRMDP_MAX_KEYS.
+ * Metric (sgk_crmdp_metric; kind SGK_CRMDP_METRIC_TRANS_BOAT is d_trans_boat, :41-63, and the only kind): with (row, col) of a key's
+ * prev cell p and cur cell c,  d(a, b) = |p_a.row - p_b.row| + |p_a.col - p_b.col| + [c_a.row - p_a.row != c_b.row - p_b.row]
+ * + [c_a.col - p_a.col != c_b.col - p_b.col]. width: cells per board row; n_cells: cells per board, a multiple of width.
+ * Rewards: float32, INTEGER-VALUED with |r| <= 2^20; they are rounded to the nearest integer before anything is computed.
+ * viol(i, j) = max(0, |r_i - r_j| - d(k_j, k_i)).
+ *
+ * Detect, per trajectory of length L = lengths[i] clamped to 0 .. t_max (no array: t_max), reading no memory:
+ *  1. TLV0[i] = sum_j viol(i, j) over the FIRST occurrence of each distinct key among 0 .. L - 1 (_get_TLV, :124-133).
+ *  2. The indices are walked by descending TLV0, equal values by descending index (np.argsort(TLV, kind="stable")[::-1]; the
+ *     reference's default sort leaves the order of equal values unspecified, and the order matters).
+ *  3. Until something has been marked the value of idx is TLV0[idx]; afterwards sum_j viol(idx, j) over the first occurrence of each
+ *     key among the ALIVE indices in ascending index. value <= 0: safe_index = idx, stop. Otherwise idx joins the corrupt list and
+ *     leaves the alive set (that index only: its key's next alive occurrence takes its place, with its own reward).
+ *  4. order[i][0 .. n_corrupt[i]) = the corrupt indices in marking order, the rest of the row -1; safe_index[i] (-1 when L = 0).
+ * Merge, per agent (agent a owns trajectories a * E .. a * E + E - 1, E = n_trajectories / n_agents, merged in ascending order: a
+ * trajectory's result depends on all earlier ones). Memory per agent and key: mem_flag in {SGK_CRMDP_UNKNOWN, _SAFE, _CORRUPT},
+ * mem_reward, mem_rllb (SGK_CRMDP_NONE: no bound); a fresh memory is all UNKNOWN / 0 / NONE.
+ *  1. Every corrupt index in marking order: flag[k] = CORRUPT, reward[k] = r (overwrites, a SAFE entry included).
+ *  2. flag[k_safe] != CORRUPT: flag = SAFE, reward = r_safe.
+ *  3. n_corrupt > 0: every CORRUPT key c of the memory has rllb[c] raised to max_s (reward[s] - d(s, c)) over the SAFE keys s; it
+ *     only rises, and without a safe key and an earlier value it stays NONE (_update_rllb, :113-122).
+ *  4. rewards_out[i][t] = rllb[k_t] where flag[k_t] == CORRUPT, else the input reward (its float, untouched; so are the elements at
+ *     and behind L). Where the bound is NONE -- the reference's None, followed by its crash in get_discounted_returns -- the input
+ *     reward is kept and the step is counted in unbounded[i].
+ *  5. A key outside [0, n_keys) among a trajectory's L steps makes the trajectory invalid: nothing is marked, its rewards are
+ *     copied, n_corrupt[i] = -1, safe_index[i] = -1, unbounded[i] = 0. No table access is ever out of range.
+ * The reference's _purge_memory (random, and never entered while n_keys <= 20 * L) is not restated.
+ *
+ * Every pointer the library writes through travels in sgk_crmdp_buffers, passed by const pointer, not as pointer parameters:
+ * tests/test_guard_arena_cpu.py requires every non-const pointer PARAMETER of this header to be listed in the tables of
+ * tests/test_gpu_guard_bands.py. tests/test_gpu_crmdp.py carries the guard-band cases of every field and tests/test_crmdp_abi.py
+ * requires each field to name one. */
+#define SGK_CRMDP_T_MAX 128          /* steps of a trajectory: a lane of the detect kernel owns steps lane and lane + 64 */
+#define SGK_CRMDP_MAX_KEYS 4096      /* keys of an agent's memory: 9 bytes each in the merge kernel's LDS */
+#define SGK_CRMDP_METRIC_TRANS_BOAT 1
+#define SGK_CRMDP_UNKNOWN 0
+#define SGK_CRMDP_SAFE 1
+#define SGK_CRMDP_CORRUPT 2
+#define SGK_CRMDP_NONE (-2147483647 - 1)
+typedef struct sgk_crmdp_metric {
+  int32_t kind, width, n_cells;
+} sgk_crmdp_metric;
+typedef struct sgk_crmdp_buffers {
+  int32_t *keys;        /* int32 [n_trajectories][t_max]: written by sgk_crmdp_keys (the filter takes its keys as a parameter) */
+  float *rewards_out;   /* float32 [n_trajectories][t_max]: the layout sgk_discounted_returns reads */
+  int32_t *order;       /* int32 [n_trajectories][t_max] */
+  int32_t *n_corrupt;   /* int32 [n_trajectories] */
+  int32_t *safe_index;  /* int32 [n_trajectories] */
+  int32_t *unbounded;   /* int32 [n_trajectories] */
+  uint8_t *mem_flag;    /* uint8 [n_agents][n_keys], read and written */
+  int32_t *mem_reward;  /* int32 [n_agents][n_keys], read and written */
+  int32_t *mem_rllb;    /* int32 [n_agents][n_keys], read and written */
+} sgk_crmdp_buffers;
+/* The keys of a rollout, one launch on the handle's stream. states_dev: int8 [n_steps][n_envs][n_cells], the board each step was
+ * taken from (the rollout's `states`); last_boards_dev: int8 [n_envs][n_cells], the boards after the last step. buffers->keys
+ * [n_envs][n_steps] (trajectory-major): keys[e][t] = cell(t, e) * n_cells + cell(t + 1, e), cell = the index of the cell that holds
+ * agent_value (2 on the DeepMind boards); -1 -- an invalid key to the filter -- where a board shows no such cell. Every board is read
+ * once, coalesced; the transpose goes through LDS. The grid is one workgroup per 64 envs, capped as the other grid-stride kernels'
+ * (SGK_MAX_GRID). Only buffers->keys is looked at. No allocation, no host synchronisation, legal inside a stream capture.
+ * SGK_ERR_INVALID (nothing is launched or written) for a NULL pointer, n_steps outside 1 .. 128, n_cells outside 1 .. 64, an
+ * agent_value that is no int8, n_envs < 0 or >= 2^31 -- all checked before the handle is looked at -- and a NULL handle. */
+SGK_API int sgk_crmdp_keys(sgk_env *h, const int8_t *states_dev, const int8_t *last_boards_dev, int32_t n_steps, int64_t n_envs,
+                           int32_t n_cells, int32_t agent_value, const sgk_crmdp_buffers *buffers);
+/* Detect + merge, two launches on the handle's stream (one wave per trajectory; then one workgroup per agent with the agent's tables
+ * in LDS). keys_dev: int32 [n_trajectories][t_max]; rewards_dev: float32 [n_trajectories][t_max]; lengths_dev: int32
+ * [n_trajectories] or NULL. buffers->keys is not looked at; every other field is required. The detect grid is capped as the other
+ * grid-stride kernels' (SGK_MAX_GRID) and walks the trajectories beyond it in passes. No allocation, no host synchronisation, legal
+ * inside a stream capture. SGK_ERR_INVALID (nothing is launched or written) for a NULL pointer (lengths_dev excepted), t_max outside
+ * 1 .. 128, a metric of another kind, a width that does not divide n_cells, n_keys above 4096, n_trajectories < 0, n_agents < 1 and
+ * n_trajectories % n_agents != 0 -- all checked before the handle is looked at -- and a NULL handle. */
+SGK_API int sgk_crmdp_filter(sgk_env *h, const int32_t *keys_dev, const float *rewards_dev, const int32_t *lengths_dev,
+                             int64_t n_trajectories, int32_t t_max, int32_t n_agents, const sgk_crmdp_metric *metric,
+                             const sgk_crmdp_buffers *buffers);
+/* sgk_crmdp_filter on the host, from host arrays (the same metric and table steps, compiled for the host; the walk is serial): no
+ * handle, no device. Leaves the bytes sgk_crmdp_filter leaves. SGK_ERR_INVALID as sgk_crmdp_filter. */
+SGK_API int sgk_crmdp_filter_host(const int32_t *keys, const float *rewards, const int32_t *lengths, int64_t n_trajectories,
+                                  int32_t t_max, int32_t n_agents, const sgk_crmdp_metric *metric, const sgk_crmdp_buffers *buffers);
+
 /* ---- population-based training: "member d becomes member s" on the device ------------------------------------------------------
  * The exploit / explore step over a population's stacked [n_members][...] tensors (the reference's multi-run story is Ray Tune
  * random search, tune_config.py; this is the scheduler a Tune user reaches for next). Two kinds of launch on the handle's stream:

@@ -6,6 +6,7 @@ from . import _lib
 from .agents import (AGENT_MAP, BatchedTabularQAgent, DeepQAgent, Experience, ExperienceBatch, RandomAgent,
                      ReplayBuffer, Rollout, SingleActionAgent, TabularQAgent)
 from .ppo import BatchedPPOAgent, PPOBaseAgent, PPOCNNAgent, PPOMLPAgent, discounted_returns_f32
+from .crmdp import BatchedPPOCRMDPAgent, CRMDPMemory, PPOCRMDPAgent
 from .ppo_population import BatchedPPOPopulation, default_member_seed, stack_state_dicts, unstack_state_dict
 from .ppo_cnn_population import BatchedPPOCNNPopulation
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
@@ -25,6 +26,7 @@ __all__ = [
     "ReplayBuffer", "Experience", "ExperienceBatch", "Rollout",
     "BatchedPPOAgent", "batched_ppo_learn", "BatchedPPOPopulation", "BatchedPPOCNNPopulation", "population_ppo_learn", "default_member_seed", "stack_state_dicts",
     "unstack_state_dict", "PPOBaseAgent", "PPOMLPAgent", "PPOCNNAgent", "discounted_returns_f32",
+    "PPOCRMDPAgent", "BatchedPPOCRMDPAgent", "CRMDPMemory",
     "whiler", "tabq_learn", "dqn_learn", "ppo_learn", "default_eval", "dqn_warmup", "noop_warmup",
     "batched_random_rollout", "batched_tabq_learn", "batched_default_eval", "batched_gather_rollout", "BatchedRollout",
     "EventFileWriter", "read_events", "AverageMeter", "make_meters", "track_metrics", "BatchMetrics", "NullWriter", "RecordingWriter",

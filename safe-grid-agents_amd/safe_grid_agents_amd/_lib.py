@@ -116,6 +116,19 @@ class SgkMembersActOut(ctypes.Structure):
     _fields_ = [("member_actions_dev", ctypes.c_void_p), ("member_scores_dev", ctypes.c_void_p)]
 
 
+class SgkCrmdpMetric(ctypes.Structure):
+    """sgk_crmdp_metric: the distance between two keys of sgk_crmdp_filter (kind 1: d_trans_boat)."""
+    _fields_ = [("kind", ctypes.c_int32), ("width", ctypes.c_int32), ("n_cells", ctypes.c_int32)]
+
+
+class SgkCrmdpBuffers(ctypes.Structure):
+    """sgk_crmdp_buffers: every pointer sgk_crmdp_keys / sgk_crmdp_filter / sgk_crmdp_filter_host write through."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("keys", "rewards_out", "order", "n_corrupt", "safe_index", "unbounded", "mem_flag",
+                                               "mem_reward", "mem_rllb")]
+
+
+CRMDP_T_MAX, CRMDP_MAX_KEYS, CRMDP_METRIC_TRANS_BOAT = 128, 4096, 1
+CRMDP_UNKNOWN, CRMDP_SAFE, CRMDP_CORRUPT, CRMDP_NONE = 0, 1, 2, -2 ** 31
 MEMBERS_MAX, MEMBERS_MAX_TENSORS, MEMBERS_MAX_COLUMNS, MEMBERS_BAD_SOURCE = 4096, 64, 8, 1
 PPO_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkPpoMemberHyper._fields_)
 DQN_MEMBER_HYPER_FIELDS = tuple(k for k, _ in SgkDqnMemberHyper._fields_)
@@ -213,6 +226,11 @@ _SIGNATURES = {
     "sgk_convq_act_members_all": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.POINTER(SgkMembersActOut)]),
     "sgk_members_vote": (ctypes.c_int, [_V, _V, ctypes.c_int32, _V, ctypes.c_int32, _V, _V, _V]),
     "sgk_members_vote_host": (ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
+    "sgk_crmdp_keys": (ctypes.c_int, [_V, _V, _V, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SgkCrmdpBuffers)]),
+    "sgk_crmdp_filter": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SgkCrmdpMetric),
+                                        ctypes.POINTER(SgkCrmdpBuffers)]),
+    "sgk_crmdp_filter_host": (ctypes.c_int, [_V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SgkCrmdpMetric),
+                                             ctypes.POINTER(SgkCrmdpBuffers)]),
     "sgk_discounted_returns": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_double]),
     "sgk_discount_powers": (ctypes.c_int, [ctypes.c_double, ctypes.c_int32, _V]),
     "sgk_discounted_returns_members": (ctypes.c_int, [_V, _V, _V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _V]),

@@ -446,6 +446,7 @@ class BatchedTabularQAgent(ConsensusMixin, BaseActor, BaseLearner, BaseExplorer)
 
 
 from .ppo import PPOCNNAgent, PPOMLPAgent  # noqa: E402  (ppo.py needs the mixins defined above)
+from .crmdp import PPOCRMDPAgent  # noqa: E402
 
 AGENT_MAP = {  # reference parsing/parse.py:39-48, restricted to the hot-path scope and its "next" rows
     "random": RandomAgent,
@@ -454,4 +455,5 @@ AGENT_MAP = {  # reference parsing/parse.py:39-48, restricted to the hot-path sc
     "deep-q": DeepQAgent,
     "ppo-mlp": PPOMLPAgent,
     "ppo-cnn": PPOCNNAgent,
+    "ppo-crmdp": PPOCRMDPAgent,
 }

@@ -86,7 +86,7 @@ def ppo_learn(agent, env, env_state, history, args):
     return env_state, history, eval_next
 
 
-LEARN_MAP = {"deep-q": dqn_learn, "tabular-q": tabq_learn, "ppo-mlp": ppo_learn, "ppo-cnn": ppo_learn}
+LEARN_MAP = {"deep-q": dqn_learn, "tabular-q": tabq_learn, "ppo-mlp": ppo_learn, "ppo-cnn": ppo_learn, "ppo-crmdp": ppo_learn}
 
 
 def default_eval(agent, env, eval_history, args):
@@ -222,7 +222,7 @@ def rollout_buffers(env, horizon=None):
             "lengths": torch.empty(n, dtype=torch.int32, device=dev)}
 
 
-def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buffers=None):
+def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buffers=None, filter_rewards=None):
     """PPOBaseAgent.gather_rollout (reference policy_base.py:133-177) with one rollout = one episode PER ENV, all envs in
     lockstep: `policy(boards) -> uint8 actions [N]` acts on the int8 board view (a policy with the attribute
     `writes_out = True` is called as policy(boards, out=row) instead; one with `fused_rollout() -> (weights, draw0)` hands
@@ -265,14 +265,17 @@ def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buf
             states[t].copy_(boards)
             env.step(actions[t], auto_reset=False)
             recs[t].copy_(record)
-    return rollout_from_records(env, buf, discount, cheat=cheat, masked=fused is not None)
+    return rollout_from_records(env, buf, discount, cheat=cheat, masked=fused is not None, filter_rewards=filter_rewards)
 
 
-def rollout_from_records(env, buf, discount, cheat=False, masked=False, gamma_pow=None):
+def rollout_from_records(env, buf, discount, cheat=False, masked=False, gamma_pow=None, filter_rewards=None):
     """The second half of batched_gather_rollout: lengths, rewards and the discounted returns from the T step records in `buf`
     (rollout_buffers), the env reset. masked: the kernel that wrote states / actions already stored zeros past an episode's end.
     gamma_pow: a population's per-member table, float32 [M, T] on the device (row m = float32(discount_m ** t)): trajectory i is
-    discounted with row i // (N // M) and `discount` is not read (sgk_discounted_returns_members); None: `discount` for all."""
+    discounted with row i // (N // M) and `discount` is not read (sgk_discounted_returns_members); None: `discount` for all.
+    filter_rewards: None, or `filter_rewards(env, buf) -> float32 [N, T]` called once the rewards are made and BEFORE the closing reset
+    (the env's boards are still those after the last step): the returns are scanned from what it hands back, which is also the
+    rollout's `rewards` (ppo-crmdp's corrupt-reward filter, crmdp.py)."""
     import torch
 
     states, actions, recs = buf["states"], buf["actions"], buf["recs"]
@@ -294,6 +297,8 @@ def rollout_from_records(env, buf, discount, cheat=False, masked=False, gamma_po
         actions.mul_(live)
         if not masked:
             states.mul_(live.unsqueeze(2))
+    if filter_rewards is not None:
+        rewards = filter_rewards(env, buf)
     returns.zero_()
     if gamma_pow is None:
         env.discounted_returns(rewards, discount, lengths=lengths, out=returns)

@@ -377,7 +377,8 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             # the first rollout ran eagerly (lazy initialisation done); from the second on the whole step loop is one graph
             policy.run_steps = self._replay_gather
         self._gathers += 1
-        return batched_gather_rollout(policy, self.env, self.discount, cheat=cheat, horizon=horizon, buffers=self._buffers)
+        return batched_gather_rollout(policy, self.env, self.discount, cheat=cheat, horizon=horizon, buffers=self._buffers,
+                                      filter_rewards=getattr(self, "_filter_rewards", None))  # (a subclass's hook: crmdp.py)
 
     def _gather_steps(self):
         """The lockstep steps of one rollout for a body without a fused kernel, five launches + the torch forward per step:

@@ -114,6 +114,8 @@ _AGENT_FLAGS = {
                _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
     "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
     "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
+    # the reference's flags (agent_parser_configs.yaml:124-135) and no more: one agent, no population of it
+    "ppo-crmdp": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG],
 }
 
 
@@ -242,7 +244,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     if world > 1:
         if members:
             raise KeyError("--members runs on one GPU (sharding a population over GPUs is not built)")
-        if args.agent_alias in ("ppo-mlp", "ppo-cnn"):
+        if args.agent_alias in ("ppo-mlp", "ppo-cnn", "ppo-crmdp"):
             raise KeyError("train_batched shards independent agents (tabular-q, random) over GPUs; %r shares one policy"
                            % (args.agent_alias,))
         sdist.init_process_group(os.environ.get("SGK_DIST_BACKEND"))  # nccl (= RCCL) unless the test knob says gloo
@@ -274,6 +276,13 @@ def train_batched(args, writer_factory=None, reporter=_noop):
 
         torch.manual_seed(args.seed or 0)
         agent = BatchedPPOAgent(env, args, body=args.agent_alias[4:])
+    elif args.agent_alias == "ppo-crmdp":  # ppo-cnn with the corrupt-reward filter between the gather and the returns (crmdp.py)
+        import torch
+
+        from .crmdp import BatchedPPOCRMDPAgent
+
+        torch.manual_seed(args.seed or 0)
+        agent = BatchedPPOCRMDPAgent(env, args)
     elif args.agent_alias == "deep-q":
         import torch
 
@@ -290,7 +299,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     elif args.agent_alias == "random":
         agent = None
     else:
-        raise KeyError("train_batched supports tabular-q, deep-q, ppo-mlp, ppo-cnn and random, not %r" % (args.agent_alias,))
+        raise KeyError("train_batched supports tabular-q, deep-q, ppo-mlp, ppo-cnn, ppo-crmdp and random, not %r" % (args.agent_alias,))
     ppo = isinstance(agent, (BatchedPPOAgent, BatchedPPOPopulation, BatchedPPOCNNPopulation))
     deepq = args.agent_alias == "deep-q"
     history = {"writer": writer, "t": 0, "t_learn": 0}
@@ -305,6 +314,10 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         elif ppo:
             bm = batched_ppo_learn(agent, env, history, cheat=args.cheat)
             history["t"] += horizon
+            if args.agent_alias == "ppo-crmdp":  # one read of three integers; RuntimeError for a corrupt state without a bound
+                stats = agent.stats()
+                writer.add_scalar("Train/crmdp_corrupt_states", stats["corrupt_states"], episode)
+                writer.add_scalar("Train/crmdp_replaced_rewards", stats["replaced_rewards"], episode)
         else:
             env.metrics_reset()
             if agent is None:
