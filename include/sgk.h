@@ -86,6 +86,7 @@ extern "C" {
  *                       kernel record per launch).
  *   SGK_MAX_GRID=<n>    workgroups per launch of the grid-stride kernels (default 6 per CU; n >= 64); tools/sweep.py.
  *   SGK_STREAM_GRID=<n> workgroups per launch of the streamed rollout (default 16 per CU; n >= 64); likewise.
+ *   SGK_ROLLOUT_GRID=<n> workgroups per launch of the outputs-once rollout (default 12 per CU; n >= 64); the grid-pass tests cap it.
  *   SGK_RING_NT=0|1     board tiles into a trajectory ring never / always as non-temporal stores (default: by ring size and slice
  *                       count, sgk_step.hip: ring_stores_nt); the A/B knob behind profiles/r05/ring_nt_ab.log.
  *   SGK_STEP_SERVER=0   host-visible handles of <= 64 envs serve sgk_step_host with one launch per call instead of the resident
@@ -1080,6 +1081,9 @@ SGK_API int sgk_debug_level(int env_id, int32_t dims[4], uint8_t templ[64], uint
 /* how many instantiated hipGraphs the handles hold (sgk_step_random / sgk_tabq_learn_steps keep at most 16 each, least
  * recently used dropped first); either handle and either output may be NULL */
 SGK_API int sgk_debug_graph_count(const sgk_env *h, const sgk_tabq *q, int32_t *env_graphs_out, int32_t *tabq_graphs_out);
+/* the launch geometry the handle settled on at sgk_create: out = {compute units, workgroups per launch of the grid-stride kernels
+ * (SGK_MAX_GRID), of the streamed rollout (SGK_STREAM_GRID), of the outputs-once rollout (SGK_ROLLOUT_GRID)} */
+SGK_API int sgk_debug_launch_grids(const sgk_env *h, int32_t out[4]);
 /* test hook for the step server's protocol: writes an exit word into the handle's mailbox as if a server that had left earlier
  * had its word land late (SGK_ERR_INVALID for a handle without a resident server). The next sgk_step_host / sgk_reset must still
  * take its step exactly once. */

@@ -274,6 +274,10 @@ int sgk_create_ex(int env_id, int64_t n_envs, int device, uint64_t seed, uint64_
   }
   // the outputs-once rollout is issue-bound and register-light (64 VGPRs: 8 waves per SIMD fit)
   s.rollout_grid = s.n_cus * 12;  // measured at 1 M envs: 6 / 8 / 12 / 16 per CU = 0.428 / 0.450 / 0.408 / 0.411 us per step (BoatRace)
+  if (const char *rg = getenv("SGK_ROLLOUT_GRID")) {
+    int v = atoi(rg);
+    if (v >= 64) s.rollout_grid = v;
+  }
   SGK_TRY(pooled_stream(device, &h->own_stream));
   h->stream = h->own_stream;
   const int64_t n_pad = ((s.n + 255) / 256) * 256;
@@ -1871,6 +1875,16 @@ int sgk_debug_graph_count(const sgk_env *h, const sgk_tabq *q, int32_t *env_grap
   SGK_TEST_HOOK_ONLY();
   if (env_graphs_out) *env_graphs_out = h ? (int32_t)h->graphs.size() : 0;
   if (tabq_graphs_out) *tabq_graphs_out = q ? (int32_t)q->graphs.size() : 0;
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
+int sgk_debug_launch_grids(const sgk_env *h, int32_t out[4]) try {
+  SGK_TEST_HOOK_ONLY();
+  if (!h || !out) return fail(SGK_ERR_INVALID, "NULL argument");
+  out[0] = h->sh.n_cus;  // (what the environment knobs of sgk_create left behind: a knob that was ignored shows here)
+  out[1] = h->sh.max_grid;
+  out[2] = h->sh.stream_grid;
+  out[3] = h->sh.rollout_grid;
   return SGK_OK;
 } SGK_CATCH_STATUS
 

@@ -275,6 +275,7 @@ _SIGNATURES = {
     "sgk_tabq_load_shared": (ctypes.c_int, [_V, _V]),
     "sgk_tabq_consensus_host": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int64, _V, _V, _V]),
     "sgk_debug_graph_count": (ctypes.c_int, [_V, _V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "sgk_debug_launch_grids": (ctypes.c_int, [_V, _V]),
     "sgk_debug_server_stale_exit_word": (ctypes.c_int, [_V]),
     "sgk_debug_fail_host_alloc": (ctypes.c_int, [ctypes.c_int]),
     "sgk_tabq_copy_table": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int64, _V]),

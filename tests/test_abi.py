@@ -42,6 +42,7 @@ assert lib.sgk_debug_host_step(0, ctypes.c_uint64(0), 1, 1, ctypes.c_uint64(0), 
 assert lib.sgk_debug_reset_word(0, ctypes.c_uint64(0), ctypes.c_uint64(0), 1, None) == 2**64 - 1
 assert lib.sgk_debug_level(0, dims, templ, agent) == -1
 assert lib.sgk_debug_graph_count(None, None, ctypes.byref(g0), ctypes.byref(g1)) == -1 and (g0.value, g1.value) == (-7, -7)
+assert lib.sgk_debug_launch_grids(None, dims) == -1 and list(dims) == [0, 0, 0, 0]
 assert lib.sgk_debug_server_stale_exit_word(None) == -1 and b"SGK_ENABLE_TEST_HOOKS" in lib.sgk_last_error()
 assert lib.sgk_debug_fail_host_alloc(1) == -1   # refused ...
 assert lib.sgk_debug_fail_host_alloc(0) == -1   # ... and not armed: the countdown a working hook would hand back is 1, not an error

@@ -125,7 +125,8 @@ EXEMPT = _table(
      + _keys("sgk_comm_info", "rank_out", "world_out", "device_out") + _keys("sgk_allreduce_metrics", "inout_dev", "hip_stream")
      + _keys("sgk_metrics_allreduced", "out_host"), _RCCL),
     (_keys("sgk_debug_host_transition", "out") + _keys("sgk_debug_host_step", "state_word_out", "out", "aux_env")
-     + _keys("sgk_debug_level", "dims", "templ", "agent_value") + _keys("sgk_debug_graph_count", "env_graphs_out", "tabq_graphs_out"), _DEBUG),
+     + _keys("sgk_debug_level", "dims", "templ", "agent_value") + _keys("sgk_debug_graph_count", "env_graphs_out", "tabq_graphs_out")
+     + _keys("sgk_debug_launch_grids", "out"), _DEBUG),
 )
 
 

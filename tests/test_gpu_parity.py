@@ -11,6 +11,7 @@ import types
 import numpy as np
 import pytest
 
+import grid_passes as GP
 import safe_grid_agents_amd as S
 from oracle import oracle as O
 from safe_grid_agents_amd import _lib
@@ -1484,42 +1485,7 @@ def test_random_schedules_of_every_kind_of_step_stay_exact(name, plan_seed, n):
         op = rng.choice(["graph", "fused", "stream", "ring", "given", "repeat", "reset_done", "mask", "noreset"])
         k = int(rng.choice([1, 1, 2, 3, 5, 17, 64, 101]))
         what = "%s op %d: %s k=%d at t=%d" % (name, op_i, op, k, t)
-        if op in ("graph", "fused", "stream", "noreset"):
-            auto = op != "noreset"
-            env.step_random(k, auto_reset=auto, fused={"graph": False, "noreset": False, "fused": True, "stream": "stream"}[op])
-            orc.rollout(k, seed=seed, t_begin=t, auto_reset=auto)
-            t += k
-        elif op == "ring":
-            first = int(rng.randint(0, 5))
-            env.rollout_random_stream(k, boards=ring_b, recs=ring_r, first_slice=first)
-            for j in range(k):
-                rec = orc.rollout(1, seed=seed, t_begin=t + j, auto_reset=True)
-                if j >= k - 5:  # the last five steps are still in the ring
-                    sl = (first + j) % 5
-                    assert (ring_b[sl].cpu().numpy() == orc.boards()).all(), what
-                    assert (ring_r[sl].cpu().numpy() == np.asarray(rec)).all(), what
-            t += k
-        elif op == "given":
-            acts = rng.randint(0, 4, size=n).astype(np.uint8)
-            auto = bool(rng.randint(0, 2))
-            env.step(torch.as_tensor(acts, device="cuda"), auto_reset=auto)
-            orc.rollout(1, seed=seed, actions=acts[None], auto_reset=auto)
-            t += 1
-        elif op == "repeat":
-            k = min(k, 17)
-            acts = rng.randint(0, 4, size=n).astype(np.uint8)
-            env.step_repeat(torch.as_tensor(acts, device="cuda"), k, auto_reset=True)
-            orc.rollout(k, seed=seed, actions=np.repeat(acts[None], k, axis=0), auto_reset=True)
-            t += k
-        elif op == "reset_done":
-            env.reset_done()
-            for i in np.nonzero(orc.field("game_over"))[0]:
-                orc.reset(int(i))
-        else:
-            m = (rng.rand(n) < 0.2).astype(np.uint8)
-            env.reset(torch.as_tensor(m, device="cuda"))
-            for i in np.nonzero(m)[0]:
-                orc.reset(int(i))
+        t, _, _ = GP.schedule_op(env, orc, rng, op, k, t, seed, ring_b=ring_b, ring_r=ring_r, what=what)  # (tests/grid_passes.py)
         assert_same_state(env, orc, what)
     assert env.lockstep_t == t
     env.close()
