@@ -435,6 +435,71 @@ SGK_API int sgk_tabq_load_shared(sgk_tabq *q, const double *table_dev);
 SGK_API int sgk_tabq_consensus_host(const double *table_host, int64_t n_agents, int64_t n_states, const uint8_t *voters_mask_host,
                                     int64_t *votes_out_host, int64_t *voters_out_host);
 
+/* ---- the same vote on the HASHED levels (SGK_TOMATO_WATERING), by board key (csrc/sgk_tabq_hash_consensus.hip) --------------------
+ * An agent's slots are its own, so the rows do not line up by slot -- they line up by KEY: a slot's key names its board
+ * (sgk_tabq_copy_keys), and every key is below 1 << SGK_TABQ_HASH_KEY_BITS. The rule, exactly:
+ *  - agent e votes on key k iff it may (voters_mask: mask[e] != 0; NULL: every agent), one of its slots holds k, and that slot's row
+ *    has an entry that compares != 0.0; -0.0 counts as zero. A claimed slot whose row is all zeros is a defaultdict row never learnt:
+ *    no opinion. A key nobody votes on is ABSENT from the output;
+ *  - a voter's action is the same rule (the same code) as sgk_tabq_consensus: the first maximum, as np.argmax picks;
+ *  - the output is the U voted keys in ASCENDING order with their counts. Every element of keys, votes, voters and count is
+ *    OVERWRITTEN: behind the last key, keys is 0xffffffff and the counts are 0. When U > max_keys the first max_keys keys in ascending
+ *    order are written with their full counts, and *count still says U;
+ *  - a key >= 1 << SGK_TABQ_HASH_KEY_BITS other than the empty marker cannot occur; it is skipped, and nothing indexes past the bitmap.
+ * The counts are integers: the result depends neither on the grid's shape nor on the order of the atomics. No allocation, no host
+ * synchronisation, enqueued on the handle's stream: capturable in a hipGraph. The agents are only READ: tables, keys, tags, the step
+ * counter, epsilon and the overflow flag stay as they are, and no kept row is invalidated. SGK_ERR_INVALID with a message and nothing
+ * launched: a NULL handle, descriptor, keys, votes, count or workspace, max_keys < 1, a workspace below
+ * sgk_tabq_hash_consensus_workspace_bytes(q), a misaligned pointer (keys 4, votes / voters / count 8, workspace 16 bytes), a
+ * perfect-hash level (sgk_tabq_consensus is the call for it).
+ * Every output and the workspace travel in ONE descriptor passed by const pointer, as sgk_members_act_out does and for its reason:
+ * tests/test_guard_arena_cpu.py lists every non-const pointer parameter; tests/test_hash_consensus_cpu.py holds the table that names
+ * a guard-band case of tests/test_gpu_hash_consensus.py for every field. */
+#define SGK_TABQ_HASH_KEY_BITS 22 /* every key of a hashed level is < 1 << 22; 0xffffffff = empty */
+typedef struct sgk_tabq_hash_votes {
+  uint32_t *keys;          /* [max_keys]    the voted keys, ASCENDING; 0xffffffff behind the last */
+  int64_t *votes;          /* [max_keys][4] votes[j][a] = voting agents whose greedy action on board keys[j] is a; 0 behind the last */
+  int64_t *voters;         /* [max_keys] or NULL: the row sums */
+  int64_t *count;          /* [1] the number U of distinct voted keys -- the TRUE number, also when U > max_keys */
+  int64_t max_keys;        /* >= 1 */
+  void *workspace;         /* >= sgk_tabq_hash_consensus_workspace_bytes(q), 16-byte aligned; contents need not be kept */
+  int64_t workspace_bytes;
+} sgk_tabq_hash_votes;
+/* 768 KiB (the bitmap and its prefix) + 8 bytes per slot + 1 byte per slot and agent at the handle's CURRENT capacity (ask again
+ * after sgk_tabq_hash_grow). < 0: an error code (a NULL handle, a perfect-hash level). */
+SGK_API int64_t sgk_tabq_hash_consensus_workspace_bytes(sgk_tabq *q);
+SGK_API int sgk_tabq_hash_consensus(sgk_tabq *q, const uint8_t *voters_mask_dev, const sgk_tabq_hash_votes *out);
+/* The mirror: for every agent with agents_mask[e] != 0 (NULL: all) the table becomes EXACTLY the table that results from a sequential
+ * insertion: start from an empty table of the agent's current capacity, insert keys_dev[0 .. min(*count_dev, max_keys)) in the given
+ * order through the library's one probe loop, and give each key the row rows_dev[j] (float64 [max_keys][4]). So: every other slot is
+ * empty with a zero row; a later duplicate key overwrites the earlier row; the empty marker in the list is skipped; a key that finds
+ * the table full raises the sticky overflow flag (sgk_tabq_hash_info) as everywhere else and is dropped. The agent's tag becomes "no
+ * pending act, no kept row": an sgk_tabq_learn behind a load without a new sgk_tabq_act learns nothing, as for an env that was over.
+ * Agents not selected keep every byte. count_dev is read ON THE DEVICE, so vote, conversion and load chain without a host round
+ * trip. The table is built once (one workgroup) and broadcast as a streaming write. No allocation, no host synchronisation, the
+ * handle's stream: capturable; as after sgk_tabq_hash_grow the pointers do not move, so the sgk_tabq_learn_steps graphs stay valid.
+ * The insertion is a serial chain in one workgroup (the key row in LDS up to 32 768 slots, in the workspace above): its cost grows with
+ * the list, and a key that finds the table FULL costs a probe of every slot before it is dropped -- load into tables that hold the
+ * list (BatchedTabularQAgent.hash_consensus_agent sizes them), not a list several times the capacity.
+ * scratch: only workspace and workspace_bytes are read (the same size as for the vote; a vote's descriptor may be passed again once
+ * its outputs have been converted). Refusals as for the vote, plus NULL keys_dev / rows_dev / count_dev and max_keys outside
+ * 1 .. 2^31 - 1. */
+SGK_API int sgk_tabq_hash_load_shared(sgk_tabq *q, const uint8_t *agents_mask_dev, const uint32_t *keys_dev, const double *rows_dev,
+                                      const int64_t *count_dev, int64_t max_keys, const sgk_tabq_hash_votes *scratch);
+/* the vote on host arrays as sgk_tabq_copy_keys / sgk_tabq_copy_table hand them out: keys_host [n_agents][capacity], rows_host
+ * [n_agents][capacity][4]; no GPU, no handle, the same rule (the same code); out's workspace is not used. */
+SGK_API int sgk_tabq_hash_consensus_host(const uint32_t *keys_host, const double *rows_host, int64_t n_agents, int32_t capacity,
+                                         const uint8_t *voters_mask_host, const sgk_tabq_hash_votes *out);
+/* the load's table on the host: ONE agent's table of `capacity` slots (a power of two in 64 .. 2^24) behind the sequential insertion
+ * of keys_in[0 .. count) with rows_in [count][4] -- what sgk_tabq_hash_load_shared leaves in every selected agent. */
+typedef struct sgk_tabq_hash_table {
+  uint32_t *keys;      /* [capacity]    0xffffffff = empty */
+  double *rows;        /* [capacity][4] zero where the slot is empty */
+  int32_t *overflowed; /* [1] or NULL: 1 iff a key found the table full (and was dropped) */
+} sgk_tabq_hash_table;
+SGK_API int sgk_tabq_hash_load_shared_host(const uint32_t *keys_in, const double *rows_in, int64_t count, int32_t capacity,
+                                           const sgk_tabq_hash_table *out);
+
 /* ---- DeepQAgent.act_explore, batched (reference value.py:94-111) ------------------------------------------------------ */
 /* scores_dev: float32 [n_envs][4] (16-byte aligned) from the Q-network; actions_out_dev: uint8 [n_envs]. Draws from
  * Categorical(eps/4 + (1 - eps) on the argmax) with the counter RNG (Philox stream 2, keyed by global env index and

@@ -369,6 +369,17 @@ int sgk_handle_launch_site(sgk_env *h, const sgk::Shard **sh_out, hipStream_t *s
   return SGK_OK;
 } SGK_CATCH_STATUS
 
+// the same for a tabular-Q handle (sgk_tabq_hash_consensus.hip): its env's shard and stream, and its own arrays as they are now (a
+// growth moves them). Raises no flag: a caller that writes the tables says so itself.
+int sgk_tabq_launch_site(sgk_tabq *q, const sgk::Shard **sh_out, const sgk::TabqShard **tq_out, hipStream_t *stream_out) try {
+  if (!q) return fail(SGK_ERR_INVALID, "handle is NULL");
+  SGK_CHECK_HANDLE(q->env);
+  *sh_out = &q->env->sh;
+  *tq_out = &q->tq;
+  *stream_out = q->env->stream;
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_reward_scale(sgk_env *h, double *scale_out) try {
   SGK_CHECK_HANDLE(h);
   if (!scale_out) return fail(SGK_ERR_INVALID, "scale_out is NULL");

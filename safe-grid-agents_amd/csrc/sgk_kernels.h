@@ -240,6 +240,12 @@ hipError_t launch_tabq_hash_used(const Shard &sh, const TabqShard &tq, int32_t *
 hipError_t launch_tabq_hash_grow(const Shard &sh, const TabqShard &tq, uint32_t *keys_new, double *table_new, int32_t cap_new,
                                  hipStream_t st);
 hipError_t launch_tabq_learn(const Shard &sh, const TabqShard &tq, const uint8_t *actions, int cheat, hipStream_t st);
+// sgk_tabq_hash_consensus.hip: the hashed levels' vote by board key into `out` (memsets + mark, scan, count), and its mirror: ONE
+// table built by sequential insertion in `workspace`, then broadcast into the agents `mask` selects (keys, rows, tags)
+hipError_t launch_tabq_hash_consensus(const Shard &sh, const TabqShard &tq, const uint8_t *mask, const sgk_tabq_hash_votes &out,
+                                      hipStream_t st);
+hipError_t launch_tabq_hash_load_shared(const Shard &sh, const TabqShard &tq, const uint8_t *mask, const uint32_t *keys_in,
+                                        const double *rows, const int64_t *count_dev, int64_t max_keys, void *workspace, hipStream_t st);
 // one lockstep step of tabq_learn in one launch (act_explore, env.step, learn, reset of the finished envs); actions_out may be null
 hipError_t launch_tabq_step(const Shard &sh, const TabqShard &tq, int cheat, uint32_t flags, uint8_t *actions_out, hipStream_t st);
 hipError_t launch_tabq_rollout(const Shard &sh, const TabqShard &tq, int64_t n_steps, int cheat, hipStream_t st);

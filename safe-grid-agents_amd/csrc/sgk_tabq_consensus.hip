@@ -8,11 +8,13 @@
 //   tabq_voters_kernel  voters[state] = the sum of votes[state][.] (only behind the shared-state form; the other writes it itself)
 //   tabq_load_kernel    the mirror: every agent's row of a state := the shared table's row, 16-byte stores, a wave's 1 KB contiguous
 // The counts are integers: the result does not depend on the grid's shape or on the order of the atomics.
-// The vote's rule (vote_of_row) is shared with the host restatement below, which needs no GPU.
+// The vote's rule (vote_of_row, sgk_tabq_vote.h) is shared with the host restatement below, which needs no GPU, and with the hashed
+// levels' vote by board key (sgk_tabq_hash_consensus.hip).
 #include <hip/hip_runtime.h>
 
 #include "sgk_host_core.h"
 #include "sgk_kernels.h"
+#include "sgk_tabq_vote.h"
 
 using sgk::host::fail;
 
@@ -23,18 +25,6 @@ namespace {
 constexpr int VOTE_WG = 256;           // four waves
 constexpr int VOTE_UNROLL = 4;         // rows a lane has in flight: 8 x 16 bytes
 constexpr int64_t VOTE_TARGET_WGS = 2048;  // 256 CUs x 8 resident workgroups: what a 25-state level and a 1 296-state level both reach
-
-// A row's vote: -1 for a row that is all zeros (either sign: a row the agent never learnt, the reference's fresh defaultdict row,
-// whose argmax of 0 is no opinion), else the greedy action of sgk_tabq_act(explore = 0) -- the first maximum, as np.argmax picks.
-__host__ __device__ __forceinline__ int vote_of_row(double q0, double q1, double q2, double q3) {
-  if (!(q0 != 0.0 || q1 != 0.0 || q2 != 0.0 || q3 != 0.0)) return -1;
-  int best = 0;
-  double bv = q0;
-  if (q1 > bv) { bv = q1; best = 1; }
-  if (q2 > bv) { bv = q2; best = 2; }
-  if (q3 > bv) { bv = q3; best = 3; }
-  return best;
-}
 
 // How the (state, agent) plane is cut into workgroups: `chunks` workgroups per state, each a run of `per` agents -- a whole number of
 // the workgroup's passes (256 lanes x 4 rows in flight = 1 024 agents), so every pass but the batch's last is full and every wave's 64

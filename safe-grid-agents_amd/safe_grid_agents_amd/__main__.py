@@ -4,7 +4,7 @@ default log dir runs/<env>/<agent>/<baseline|corrupt>/<seed>."""
 import os
 import random
 
-from .consensus import check_consensus_eval
+from .consensus import check_consensus_eval, check_hash_consensus_eval
 from .ensemble import check_ensemble_eval
 from .pbt import parse_pbt
 from .trainer import members_n_envs, prepare_parser, sweep_grid, train, train_batched
@@ -34,6 +34,7 @@ def main(argv=None):
     sweep_grid(args)  # --sweep: stops here, with the valid names, when it cannot run (no --members, an unknown name, M % G != 0)
     check_ensemble_eval(args)  # --ensemble-eval: stops here when it cannot run (no --members, a population without the ensemble)
     check_consensus_eval(args)  # --consensus-eval: stops here when it cannot run (not tabular-q, tomato, -N < 2, more than one device)
+    check_hash_consensus_eval(args)  # --hash-consensus-eval: stops here when it cannot run (not tomato, not tabular-q, -N < 2, devices)
     if getattr(args, "devices", 1) > 1 and "WORLD_SIZE" not in os.environ:
         if getattr(args, "n_envs", 0) <= 0:
             raise SystemExit("--devices shards the batched trainer: give -N/--n-envs too")

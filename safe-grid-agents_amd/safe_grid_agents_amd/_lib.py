@@ -116,6 +116,17 @@ class SgkMembersActOut(ctypes.Structure):
     _fields_ = [("member_actions_dev", ctypes.c_void_p), ("member_scores_dev", ctypes.c_void_p)]
 
 
+class SgkTabqHashVotes(ctypes.Structure):
+    """sgk_tabq_hash_votes: every output of sgk_tabq_hash_consensus and its workspace."""
+    _fields_ = [("keys", ctypes.c_void_p), ("votes", ctypes.c_void_p), ("voters", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("max_keys", ctypes.c_int64), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
+
+
+class SgkTabqHashTable(ctypes.Structure):
+    """sgk_tabq_hash_table: the outputs of sgk_tabq_hash_load_shared_host."""
+    _fields_ = [("keys", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("overflowed", ctypes.c_void_p)]
+
+
 class SgkCrmdpMetric(ctypes.Structure):
     """sgk_crmdp_metric: the distance between two keys of sgk_crmdp_filter (kind 1: d_trans_boat)."""
     _fields_ = [("kind", ctypes.c_int32), ("width", ctypes.c_int32), ("n_cells", ctypes.c_int32)]
@@ -274,6 +285,11 @@ _SIGNATURES = {
     "sgk_tabq_consensus": (ctypes.c_int, [_V, _V, _V, _V]),
     "sgk_tabq_load_shared": (ctypes.c_int, [_V, _V]),
     "sgk_tabq_consensus_host": (ctypes.c_int, [_V, ctypes.c_int64, ctypes.c_int64, _V, _V, _V]),
+    "sgk_tabq_hash_consensus_workspace_bytes": (ctypes.c_int64, [_V]),
+    "sgk_tabq_hash_consensus": (ctypes.c_int, [_V, _V, ctypes.POINTER(SgkTabqHashVotes)]),
+    "sgk_tabq_hash_load_shared": (ctypes.c_int, [_V, _V, _V, _V, _V, ctypes.c_int64, ctypes.POINTER(SgkTabqHashVotes)]),
+    "sgk_tabq_hash_consensus_host": (ctypes.c_int, [_V, _V, ctypes.c_int64, ctypes.c_int32, _V, ctypes.POINTER(SgkTabqHashVotes)]),
+    "sgk_tabq_hash_load_shared_host": (ctypes.c_int, [_V, _V, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(SgkTabqHashTable)]),
     "sgk_debug_graph_count": (ctypes.c_int, [_V, _V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "sgk_debug_launch_grids": (ctypes.c_int, [_V, _V]),
     "sgk_debug_server_stale_exit_word": (ctypes.c_int, [_V]),

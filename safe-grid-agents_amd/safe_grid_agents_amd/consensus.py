@@ -15,7 +15,18 @@ under the first-max rule IS the plurality vote with np.argmax's tie rule, and a 
 evaluate_consensus() (the consensus agent through the existing fused evaluation, sgk_tabq_eval). The source agent is only read: its
 tables, step counter and epsilon stay as they were, and the consensus agent acts on an env handle of its own.
 
-This module also holds the command line's side: --consensus-eval (check_consensus_eval: SystemExit with a plain message).
+On TomatoWatering every agent keeps a HASH table of its own, so the rows do not line up by slot; they line up by board key
+(csrc/sgk_tabq_hash_consensus.hip):
+
+  sgk_tabq_hash_consensus    the same vote per board key: a 2^22-bit presence bitmap + prefix popcount rank the voted keys, the output
+                             is the U voted keys ascending with their counts and U itself on the device
+  sgk_tabq_hash_load_shared  the mirror: the selected agents' tables := the one table a sequential insertion of (key, row) pairs leaves
+
+hash_consensus() / load_shared_hash_table() / hash_consensus_agent() / evaluate_hash_consensus() are the four methods again under new
+names; the old ones keep refusing the level.
+
+This module also holds the command line's side: --consensus-eval and --hash-consensus-eval (check_consensus_eval,
+check_hash_consensus_eval: SystemExit with a plain message).
 """
 import ctypes
 
@@ -148,12 +159,199 @@ class ConsensusMixin:
 
     def _close_consensus(self):
         cache, self._consensus_cache = self._consensus_cache, None
-        for st in (cache or {}).values():
+        hashed, self._hash_consensus_cache = self._hash_consensus_cache, None
+        self._hash_consensus_buffers = None
+        for st in list((cache or {}).values()) + list((hashed or {}).values()):
             agent = st.get("agent")
             if agent is not None:
                 env = agent.env
                 agent.close()
                 env.close()
+
+    # -- the hashed levels (TomatoWatering): the vote by board key ---------------------------------------------------------------------
+    _hash_consensus_cache = None    # n_envs -> {"agent", "rows"}: evaluate_hash_consensus()'s twin, made once
+    _hash_consensus_buffers = None  # the default outputs and the workspace of hash_consensus(), made once per capacity
+
+    HASH_CONSENSUS_MAX_KEYS = 1 << 18
+
+    def _hash_consensus_level(self):
+        if self.env.info.env_id != _lib.TOMATO_WATERING:
+            raise ValueError("%s has a perfect hash of its boards: its agents' rows line up by state and consensus() is the vote; "
+                             "hash_consensus() is for the levels with a hash table per agent" % self.env.name)
+
+    def _hash_workspace(self):
+        """(uint8 workspace of the size the library asks for at the current capacity, its size): made once, again after a growth."""
+        import torch
+
+        need = int(self.lib.sgk_tabq_hash_consensus_workspace_bytes(self._h))
+        if need < 0:
+            _lib.check(need)
+        st = self._hash_consensus_buffers
+        if st is None:
+            st = self._hash_consensus_buffers = {}
+        ws = st.get("workspace")
+        if ws is None or ws.numel() < need:
+            ws = st["workspace"] = torch.empty(need, dtype=torch.uint8, device="cuda:%d" % self.env.device)
+        return ws, need
+
+    def hash_consensus(self, mask=None, max_keys=None, out=None):
+        """The agents' vote on every board some agent has an opinion on (sgk_tabq_hash_consensus: memsets and three launches, no host
+        synchronisation) -> HashedConsensus: the voted keys ascending, their counts, and their number on the device. mask: uint8 or bool
+        [N], agent e may vote iff mask[e] != 0 (default: everyone). max_keys: rows of the outputs (default min(N * capacity, 2^18));
+        with fewer rows than voted keys the first max_keys keys are written and count still tells the true number. out: a
+        HashedConsensus whose tensors are written again (its max_keys holds). The default outputs and the workspace are made once per
+        agent and reused: a later call overwrites the result of an earlier one. ValueError on a level with a perfect hash and for a
+        tensor of the wrong device, dtype or shape."""
+        import torch
+
+        self._hash_consensus_level()
+        env = self.env
+        if mask is not None:
+            mask = env._check(mask, "mask", shape=(env.n_envs,), dtypes=("uint8", "bool"))
+        dev = "cuda:%d" % env.device
+        if out is not None:
+            if max_keys is not None and int(max_keys) != out.max_keys:
+                raise ValueError("max_keys is %d but out has %d rows" % (int(max_keys), out.max_keys))
+            K = out.max_keys
+            keys = env._check(out.keys, "out.keys", shape=(K,), dtypes=("int32",))
+            votes = env._check(out.votes, "out.votes", shape=(K, 4), dtypes=("int64",))
+            voters = env._check(out.voters, "out.voters", shape=(K,), dtypes=("int64",))
+            count = env._check(out.count, "out.count", shape=(1,), dtypes=("int64",))
+        else:
+            K = min(env.n_envs * self.n_states, self.HASH_CONSENSUS_MAX_KEYS) if max_keys is None else int(max_keys)
+            if K < 1:
+                raise ValueError("max_keys must be >= 1, not %d" % K)
+            ws, _ = self._hash_workspace()
+            st = self._hash_consensus_buffers
+            if st.get("max_keys") != K:
+                st.update(max_keys=K, keys=torch.empty(K, dtype=torch.int32, device=dev), votes=torch.empty((K, 4), dtype=torch.int64, device=dev),
+                          voters=torch.empty(K, dtype=torch.int64, device=dev), count=torch.empty(1, dtype=torch.int64, device=dev))
+            keys, votes, voters, count = st["keys"], st["votes"], st["voters"], st["count"]
+        ws, need = self._hash_workspace()
+        desc = _lib.SgkTabqHashVotes(keys.data_ptr(), votes.data_ptr(), voters.data_ptr(), count.data_ptr(), K, ws.data_ptr(), need)
+        env._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_tabq_hash_consensus(self._h, None if mask is None else ctypes.c_void_p(mask.data_ptr()), ctypes.byref(desc)))
+        env._sync_lib_to_torch()
+        return HashedConsensus(keys, votes, voters, count)
+
+    def load_shared_hash_table(self, keys, rows, count=None, mask=None):
+        """The selected agents' tables := the table a sequential insertion of keys[0 .. count) with the rows rows[j] leaves
+        (sgk_tabq_hash_load_shared: three launches, no host synchronisation). keys: int32 [K] bit patterns as HashedConsensus.keys
+        holds them; rows: float64 [K, 4]; count: int64 [1] ON THE DEVICE (default: K); mask: uint8 or bool [N] (default: everyone).
+        A later duplicate key overwrites the earlier row, a key that finds the table full is dropped and raises the overflow flag, the
+        selected agents forget a pending act(); the others keep every byte."""
+        import torch
+
+        self._hash_consensus_level()
+        env = self.env
+        if getattr(keys, "dim", lambda: 0)() != 1 or keys.shape[0] < 1:
+            raise ValueError("keys must be a tensor [K] with K >= 1")
+        K = int(keys.shape[0])
+        keys = env._check(keys, "keys", shape=(K,), dtypes=("int32",))
+        rows = env._check(rows, "rows", shape=(K, 4), dtypes=("float64",))
+        if count is None:
+            count = torch.full((1,), K, dtype=torch.int64, device="cuda:%d" % env.device)
+        count = env._check(count, "count", shape=(1,), dtypes=("int64",))
+        if mask is not None:
+            mask = env._check(mask, "mask", shape=(env.n_envs,), dtypes=("uint8", "bool"))
+        ws, need = self._hash_workspace()
+        desc = _lib.SgkTabqHashVotes(None, None, None, None, 0, ws.data_ptr(), need)
+        env._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_tabq_hash_load_shared(self._h, None if mask is None else ctypes.c_void_p(mask.data_ptr()),
+                                                      ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(rows.data_ptr()),
+                                                      ctypes.c_void_p(count.data_ptr()), K, ctypes.byref(desc)))
+        env._sync_lib_to_torch()
+
+    @staticmethod
+    def _hash_capacity_for(n_keys, reserve_steps):
+        """The next power of two >= n_keys + 2 * reserve_steps + 1 (reserve_hash's bound: a step claims at most two slots), >= 64."""
+        return max(64, 1 << (int(n_keys) + 2 * int(reserve_steps)).bit_length())
+
+    def _grow_twin(self, twin, n_keys, reserve_steps):
+        need = self._hash_capacity_for(n_keys, reserve_steps)
+        if need > twin.HASH_CAPACITY_MAX:
+            raise RuntimeError("%d voted boards and %d steps need %d slots per agent, above the largest hash table of 2^24 slots"
+                               % (n_keys, reserve_steps, need))
+        if twin.n_states < need:
+            twin.grow_hash(need)
+
+    def hash_consensus_agent(self, n_envs=None, mask=None, seed=None, reserve_steps=0):
+        """consensus_agent() for the hashed levels: a fresh agent (same args) on a fresh env of the same level, created at or grown to
+        the next power of two >= U + 2 * reserve_steps + 1 slots (U voted boards; room for reserve_steps lockstep steps, in which
+        greedy acting claims slots too), every table the vote counts as float64 by board key: its greedy action on a board is the
+        plurality vote there, and a board nobody voted on reads as zeros. Reads U back once. The caller closes it and its env; this
+        agent is only read."""
+        import torch
+
+        self._hash_consensus_level()
+        cons = self.hash_consensus(mask=mask)
+        n_keys = cons.n_keys()
+        agent = self._fresh_twin(n_envs, seed)
+        try:
+            self._grow_twin(agent, n_keys, reserve_steps)
+            agent.load_shared_hash_table(cons.keys, cons.votes.to(torch.float64), cons.count)
+        except Exception:
+            env = agent.env
+            agent.close()
+            env.close()
+            raise
+        return agent
+
+    def evaluate_hash_consensus(self, eval_timesteps, n_envs=None, mask=None):
+        """evaluate_consensus() for the hashed levels -> (BatchMetrics, {"agreement", "voted_states", "voters"}): the vote, one
+        read-back of the number of voted boards, growth of the cached twin where it needs room (the boards plus two slots per step of
+        the evaluation: eval_timesteps - 1 + max_iterations steps), the load, then evaluate(). Greedy acting claims slots on this
+        level, so every call loads again: what an earlier evaluation claimed is gone. The twin is made once per n_envs (default
+        min(N, 1024)) and kept until close()."""
+        import torch
+
+        self._hash_consensus_level()
+        n = min(self.env.n_envs, 1024) if n_envs is None else int(n_envs)
+        if self._hash_consensus_cache is None:
+            self._hash_consensus_cache = {}
+        st = self._hash_consensus_cache.get(n)
+        if st is None:
+            st = self._hash_consensus_cache[n] = {"agent": self._fresh_twin(n), "rows": None}
+        cons = self.hash_consensus(mask=mask)
+        n_keys = cons.n_keys()
+        twin = st["agent"]
+        self._grow_twin(twin, n_keys, max(int(eval_timesteps) - 1, 0) + int(twin.env.info.max_iterations))
+        if st["rows"] is None or st["rows"].shape != cons.votes.shape:
+            st["rows"] = torch.empty(cons.votes.shape, dtype=torch.float64, device=cons.votes.device)
+        st["rows"].copy_(cons.votes)  # int64 -> float64, exact for any count a table can hold
+        twin.load_shared_hash_table(cons.keys, st["rows"], cons.count)
+        bm = twin.evaluate(eval_timesteps)
+        stats = {"agreement": cons.agreement(), "voted_states": n_keys, "voters": int(cons.voters.sum().item())}
+        return bm, stats
+
+
+class HashedConsensus:
+    """The vote of one hash_consensus() call, on the device: keys int32 [K] -- the voted boards' keys ascending, as bit patterns (-1 =
+    unused: behind the last key); votes int64 [K, 4], votes[j, a] = voting agents whose greedy action on board keys[j] is a; voters
+    int64 [K], the row sums; count int64 [1], the number U of voted boards -- the true number, also where it exceeds K. The tensors are
+    the buffers the kernels wrote."""
+
+    def __init__(self, keys, votes, voters, count):
+        self.keys, self.votes, self.voters, self.count = keys, votes, voters, count
+        self.max_keys = int(keys.shape[0])
+
+    def n_keys(self):
+        """U, read back (synchronises). RuntimeError when the outputs hold fewer rows than that."""
+        n = int(self.count.item())
+        if n > self.max_keys:
+            raise RuntimeError("%d boards were voted on but max_keys is %d: the outputs hold the first %d keys only; vote again with "
+                               "max_keys >= %d" % (n, self.max_keys, self.max_keys, n))
+        return n
+
+    policy = TabularConsensus.policy  # uint8 [K]: the first action with the most votes, 0 behind the last key
+
+    agreement = TabularConsensus.agreement
+
+    def as_dict(self):
+        """{key: [4 counts]} on the host (synchronises)."""
+        n = self.n_keys()
+        keys = (self.keys[:n].cpu().numpy().astype("int64") & 0xFFFFFFFF).tolist()
+        return dict(zip(keys, self.votes[:n].cpu().tolist()))
 
 
 # -- the command line ---------------------------------------------------------------------------------------------------------------
@@ -165,11 +363,30 @@ def check_consensus_eval(args):
     if args.agent_alias != "tabular-q":
         raise SystemExit("--consensus-eval runs on a batch of private tabular-q agents, not %r" % (args.agent_alias,))
     if args.env_alias == "tomato":
-        raise SystemExit("--consensus-eval cannot run on tomato: every agent keeps a hash table of its own, the agents' rows do not line up")
+        raise SystemExit("--consensus-eval cannot run on tomato: every agent keeps a hash table of its own, the agents' rows do not line up "
+                         "by state (--hash-consensus-eval votes by board key there)")
     if int(getattr(args, "n_envs", 0) or 0) < 2:
         raise SystemExit("--consensus-eval needs -N > 1: the consensus is the vote of the batch's private agents")
     if int(getattr(args, "devices", 1) or 1) > 1:
         raise SystemExit("--consensus-eval runs on one device: summing the votes over the ranks of --devices %d is not built" % args.devices)
+    return True
+
+
+def check_hash_consensus_eval(args):
+    """--hash-consensus-eval of `args` -> True / False. SystemExit with a plain message for an agent other than tabular-q, for a level
+    other than tomato (--consensus-eval is the flag there), without a batch of more than one agent, for more than one device, and next
+    to --consensus-eval."""
+    if not getattr(args, "hash_consensus_eval", False):
+        return False
+    if args.agent_alias != "tabular-q":
+        raise SystemExit("--hash-consensus-eval runs on a batch of private tabular-q agents, not %r" % (args.agent_alias,))
+    if args.env_alias != "tomato":
+        raise SystemExit("--hash-consensus-eval votes by board key, for tomato's hash tables: on %s the agents' rows line up by state, "
+                         "use --consensus-eval" % (args.env_alias,))
+    if int(getattr(args, "n_envs", 0) or 0) < 2:
+        raise SystemExit("--hash-consensus-eval needs -N > 1: the consensus is the vote of the batch's private agents")
+    if int(getattr(args, "devices", 1) or 1) > 1:
+        raise SystemExit("--hash-consensus-eval runs on one device: summing the votes over the ranks of --devices %d is not built" % args.devices)
     return True
 
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import envs as _envs
 from .agents import AGENT_MAP
-from .consensus import check_consensus_eval, write_consensus_eval
+from .consensus import check_consensus_eval, check_hash_consensus_eval, write_consensus_eval
 from .ensemble import check_ensemble_eval, write_ensemble_eval
 from .loops import EVAL_MAP, LEARN_MAP, WARMUP_MAP
 from .member_hyper import parse_sweep, point_label, sweep_member_hyper, sweep_table
@@ -60,6 +60,9 @@ _CORE_FLAGS = [
     # extension: with tabular-q and -N > 1 on one device, `--consensus-eval` follows every evaluation with one of the CONSENSUS agent: the
     # plurality vote, per state, of the batch's private agents (consensus.ConsensusMixin.evaluate_consensus). Absent unless given.
     ("consensus-eval", "CE", dict(action="store_true", default=argparse.SUPPRESS)),
+    # extension: the same on tomato, whose agents keep a hash table each: `--hash-consensus-eval` follows every evaluation with one of the
+    # agents' plurality vote per BOARD KEY (consensus.ConsensusMixin.evaluate_hash_consensus). Absent unless given.
+    ("hash-consensus-eval", "HCE", dict(action="store_true", default=argparse.SUPPRESS)),
 ]
 _LR = ("lr", "l", dict(type=float, required=True))
 _EPS = ("epsilon", "e", dict(type=float, default=0.01))
@@ -89,6 +92,8 @@ _PBT = [("pbt-every", "PE", dict(type=int, default=argparse.SUPPRESS)),
 _ENSEMBLE = ("ensemble-eval", "EN", dict(action="store_true", default=argparse.SUPPRESS))
 # --consensus-eval likewise (with another agent than tabular-q it parses and stops the run with a message: consensus.check_consensus_eval)
 _CONSENSUS = ("consensus-eval", "CE", dict(action="store_true", default=argparse.SUPPRESS))
+# --hash-consensus-eval likewise (consensus.check_hash_consensus_eval)
+_HASH_CONSENSUS = ("hash-consensus-eval", "HCE", dict(action="store_true", default=argparse.SUPPRESS))
 # extension, batched trainer (-N) on tomato only: `--hash-grow` grows the agents' hash tables on the device ahead of need
 # (BatchedTabularQAgent.reserve_hash before every training period and every evaluation), so that no board is ever refused and the run
 # equals the reference's unbounded dictionary whatever capacity it started with. Absent unless given; another level stops the run with a
@@ -97,7 +102,7 @@ _HASH_GROW = ("hash-grow", "HG", dict(action="store_true", default=argparse.SUPP
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
-    "tabular-q": [_LR, _EPS, _ANNEAL, _CONSENSUS, _HASH_GROW],
+    "tabular-q": [_LR, _EPS, _ANNEAL, _CONSENSUS, _HASH_CONSENSUS, _HASH_GROW],
     "deep-q": [_LR, _EPS, _ANNEAL,
                ("replay-capacity", "r", dict(type=int, default=10000)),
                ("sync-every", "s", dict(type=int, default=10000)),
@@ -232,11 +237,14 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         sweep = None  # the grid only gave the starting values: after a PBT step member m is no longer "point m % G"
     ensemble = {} if check_ensemble_eval(args) else None  # --ensemble-eval: the last ensemble evaluation's figures; SystemExit if it cannot run
     consensus = {} if check_consensus_eval(args) else None  # --consensus-eval likewise
+    if check_hash_consensus_eval(args):  # --hash-consensus-eval: the same scalars and closing line, voted by board key (tomato)
+        consensus = {"hashed": True}
     hash_grow = check_hash_grow(args)  # --hash-grow: True / False; SystemExit on a level whose tables are not hashed
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if consensus is not None and world > 1:
-        raise SystemExit("--consensus-eval runs on one device: summing the votes over %d ranks is not built" % world)
+        raise SystemExit("--%sconsensus-eval runs on one device: summing the votes over %d ranks is not built"
+                         % ("hash-" if consensus.get("hashed") else "", world))
     if getattr(args, "devices", 1) > 1 and world != args.devices:
         raise SystemExit("--devices %d needs %d ranks (WORLD_SIZE is %d): run `python -m safe_grid_agents_amd --devices %d ...`, "
                          "which starts them, or torch.distributed.run --nproc-per-node %d" % (
@@ -384,9 +392,10 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     if ensemble and rank == 0:  # one line: the last evaluation of the members voting on every env
         print("#### ENSEMBLE: %d members vote on every env; last evaluation: return %.4f safety %.4f disagreement %.4f (%d of %d votes) ####"
               % (members, ensemble["return"], ensemble["safety"], ensemble["disagreement"], ensemble["dissent"], ensemble["votes"]))
-    if consensus:  # one line: the last evaluation of the agents' plurality vote per state
-        print("#### CONSENSUS: %d agents vote on every state; last evaluation: return %.4f safety %.4f agreement %.4f (%d votes over %d states) ####"
-              % (env.n_envs, consensus["return"], consensus["safety"], consensus["agreement"], consensus["voters"], consensus["voted_states"]))
+    if consensus and "return" in consensus:  # one line: the last evaluation of the agents' plurality vote per state (tomato: per board)
+        print("#### CONSENSUS: %d agents vote on every %s; last evaluation: return %.4f safety %.4f agreement %.4f (%d votes over %d %ss) ####"
+              % (env.n_envs, "board" if consensus.get("hashed") else "state", consensus["return"], consensus["safety"], consensus["agreement"],
+                 consensus["voters"], consensus["voted_states"], "board" if consensus.get("hashed") else "state"))
     return agent, env
 
 
@@ -463,7 +472,8 @@ def _batched_eval(agent, env, args, writer, period, rank, sdist, ensemble=None, 
         # --consensus-eval: the same schedule once more with the agents' plurality vote per state as the agent. Training does not notice
         # it: the vote only reads the tables, and the consensus agent acts on an env handle of its own -- this env's metrics, reset
         # counters and state words are not touched.
-        bm, stats = agent.evaluate_consensus(args.eval_timesteps)
+        hashed = consensus.get("hashed")  # (tomato: the vote by board key, on a twin whose greedy acting claims its own slots)
+        bm, stats = (agent.evaluate_hash_consensus if hashed else agent.evaluate_consensus)(args.eval_timesteps)
         write_consensus_eval(writer, bm, stats, period)
         consensus.update(stats, **{"return": bm.meter("returns")["avg"], "safety": bm.meter("safeties")["avg"]})
     env.reset()
