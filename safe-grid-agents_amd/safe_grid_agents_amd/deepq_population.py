@@ -22,39 +22,27 @@ import torch
 
 from . import _lib
 from .deepq_batched import BatchedDeepQAgent, DeviceReplay
-from .ensemble import EnsembleMixin
-from .member_hyper import DQN_NAMES, resolve, validate_values
-from .metering import BatchMetrics
-from .pbt import PBTMixin
-from .ppo_population import FUSED_CELLS, _as_i64, default_member_seed
+from .member_hyper import DQN_NAMES
+from .population import Population, default_member_seed  # noqa: F401 (default_member_seed: importable from here as before)
+from .population import stack_state_dicts as _stack, unstack_state_dict as _unstack
+from .ppo_population import FUSED_CELLS
 
 # BatchedDeepQAgent.Q's parameters (state_dict keys, registration order) and the short names of the stacked tensors
 MEMBER_KEYS = ("0.0.weight", "0.0.bias", "1.0.0.weight", "1.0.0.bias", "2.weight", "2.bias")
 PARAMS = ("w1", "b1", "w2", "b2", "w3", "b3")
-_MASK = 2 ** 64 - 1
-_INT64_MIN = -(2 ** 63)
 
 
 def stack_state_dicts(state_dicts):
-    """Q-network state dicts (MEMBER_KEYS) -> {short name: tensor [M, ...]} in PARAMS order, one contiguous tensor per parameter.
-    Pure torch; the values are copied bit for bit."""
-    if not state_dicts:
-        raise ValueError("no members to stack")
-    out = {}
-    for key, name in zip(MEMBER_KEYS, PARAMS):
-        parts = [torch.as_tensor(sd[key]).detach().to(torch.float32) for sd in state_dicts]
-        if any(p.shape != parts[0].shape for p in parts):
-            raise ValueError("members disagree on the shape of %s" % key)
-        out[name] = torch.stack(parts).contiguous()
-    return out
+    """population.stack_state_dicts for Q-network state dicts: MEMBER_KEYS under the names PARAMS."""
+    return _stack(state_dicts, MEMBER_KEYS, PARAMS)
 
 
 def unstack_state_dict(stacked, m):
     """Member m's parameters out of stack_state_dicts' tensors, keyed like BatchedDeepQAgent.Q.state_dict() (copies)."""
-    return {key: stacked[name][m].detach().clone() for key, name in zip(MEMBER_KEYS, PARAMS)}
+    return _unstack(stacked, m, MEMBER_KEYS, PARAMS)
 
 
-class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
+class BatchedDeepQPopulation(Population):
     """M independent DeepQAgents over env's N = M x E envs (see the module docstring). ensemble_act() / evaluate_ensemble()
     (ensemble.EnsembleMixin) let the M Q-networks act as one agent on all N envs: every member votes on every env.
 
@@ -76,16 +64,15 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
 
     exploit_explore (PBTMixin) perturbs lr and discount (the learner row's columns); the three epsilon tensors are cloned only."""
 
+    HYPER_NAMES = DQN_NAMES
     PBT_COLUMNS = DQN_NAMES[:2]
-    torch = torch  # (the two BatchedDeepQAgent methods borrowed below read self.torch)
+    torch = torch # (the two BatchedDeepQAgent methods borrowed below read self.torch)
     build_Q = BatchedDeepQAgent.build_Q
 
     def __init__(self, env, args, n_members, member_seeds=None, member_keys=None, replay_slices=8, sgd_steps=1,
                  reference_loss_broadcast=True, member_hyper=None):
-        M = int(n_members)
+        M = self._member_count(env, n_members)
         hidden, layers, batch = int(getattr(args, "n_hidden", 0) or 0), int(args.n_layers), int(args.batch_size)
-        if M < 1 or env.n_envs % M:
-            raise ValueError("n_envs (%d) is not a multiple of n_members (%d): every member owns the same number of envs" % (env.n_envs, M))
         if layers != 2:
             raise ValueError("a Deep-Q population needs n_layers = 2 (the fused kernels' topology), not %d" % layers)
         if hidden not in (64, 100):
@@ -94,32 +81,14 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
             raise ValueError("a Deep-Q population needs 1 <= batch_size <= 64 (sgk_dqn_sgd_step_members), not %d" % batch)
         if env.n_cells not in FUSED_CELLS or env.action_space.n != 4:
             raise ValueError("the fused policy kernel does not cover %s (%d cells, %d actions)" % (env.name, env.n_cells, env.action_space.n))
-        self.member_values = self.hyper = None
-        if member_hyper is not None:  # (validation only, before anything touches the device)
-            self.member_values = resolve(member_hyper, DQN_NAMES, {k: float(getattr(args, k)) for k in DQN_NAMES}, M)
-        self.env, self.n_members, self.member_envs = env, M, env.n_envs // M
-        self.device = "cuda:%d" % env.device
+        self._init_members(env, args, M, member_seeds, member_keys, member_hyper)
         self.n_hidden, self.batch_size, self.sgd_steps = hidden, batch, int(sgd_steps)
         self.discount, self.lr = float(args.discount), float(args.lr)
         self.sync_every = int(args.sync_every)
         self.eps0, self.anneal = float(args.epsilon), int(args.epsilon_anneal)
         self.reference_loss_broadcast = bool(reference_loss_broadcast)
         self.t = 0  # lockstep steps taken == update_epsilon() calls == the RNG draw index
-        seed = int(getattr(args, "seed", 0) or 0)
-        self.member_seeds = [int(s) & _MASK for s in (member_seeds if member_seeds is not None
-                                                      else [default_member_seed(seed, m) for m in range(M)])]
-        keys = self.member_seeds if member_keys is None else [int(k) & _MASK for k in member_keys]
-        if len(self.member_seeds) != M or len(keys) != M:
-            raise ValueError("member_seeds / member_keys need one entry per member (%d)" % M)
-        self.member_keys = torch.tensor(_as_i64(keys), dtype=torch.int64, device=self.device)
         K0, H, dev = env.n_cells, hidden, self.device
-        if self.member_values is not None:
-            v, f64 = self.member_values, dict(dtype=torch.float64, device=dev)
-            self.hyper = {"learner": torch.tensor([[v["lr"][m], v["discount"][m]] for m in range(M)], **f64),
-                          "epsilon0": torch.tensor(v["epsilon"], **f64), "epsilon": torch.empty(M, **f64)}
-            self._one_minus_eps0 = torch.tensor([1 - e for e in v["epsilon"]], **f64)  # (the host's own 1 - eps0)
-            self._zero_eps = torch.zeros(M, **f64)
-            self._eps_t = None  # the step hyper["epsilon"] holds the values of
         self.q_body, self.action_n = "mlp", env.action_space.n  # (what build_Q reads)
         q_dicts, t_dicts = [], []
         for s in self.member_seeds:  # (on the CPU: torch.nn.Linear draws its initial weights from the CPU generator)
@@ -142,10 +111,7 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
         self.workspace = torch.zeros(env.dqn_members_workspace_bytes(H, M), dtype=torch.uint8, device=dev)
         self.replay = DeviceReplay(env.n_envs, K0, int(replay_slices), dev)
         self._actions = torch.empty((1, env.n_envs), dtype=torch.uint8, device=dev)
-        self.member_metrics = torch.empty((M, _lib.METRICS_LEN), dtype=torch.int64, device=dev)
-        self._metrics_init = torch.zeros(_lib.METRICS_LEN, dtype=torch.int64)
-        self._metrics_init[_lib.M_MAX_RETURN:_lib.M_MAX_MARGIN_POS + 1] = _INT64_MIN
-        self._metrics_init = self._metrics_init.to(dev)
+        self._alloc_member_metrics()
         self._refresh_transposes()
         self._refresh_target_transposes()
         self.reset_member_metrics()
@@ -198,37 +164,24 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
         self.member_values["epsilon"] = list(extra)
         self._eps_t = None  # (derived from the epsilon tensors: evaluated again at the next step)
 
-    def _member_index(self, m):
-        m = int(m)
-        if not 0 <= m < self.n_members:
-            raise IndexError("member %d of %d" % (m, self.n_members))
-        return m
+    def _alloc_member_hyper(self):
+        v, f64 = self.member_values, dict(dtype=torch.float64, device=self.device)
+        self.hyper = {"learner": torch.tensor([[v["lr"][m], v["discount"][m]] for m in range(self.n_members)], **f64),
+                      "epsilon0": torch.tensor(v["epsilon"], **f64), "epsilon": torch.empty(self.n_members, **f64)}
+        self._one_minus_eps0 = torch.tensor([1 - e for e in v["epsilon"]], **f64)  # (the host's own 1 - eps0)
+        self._zero_eps = torch.zeros(self.n_members, **f64)
+        self._eps_t = None  # the step hyper["epsilon"] holds the values of
 
-    def set_member_hyper(self, name, values):
-        """Member m's `name` <- values[m] (validated: ValueError), copied INTO the device tensors (no new allocation): the next step()
-        / learn_batch() -- a replay of a recorded one included -- runs with the new values. "epsilon" is the schedule's starting
-        value. A population built without member_hyper has no per-member tensors: ValueError."""
-        if self.hyper is None:
-            raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
-        if name not in DQN_NAMES:
-            raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(DQN_NAMES)))
-        vals = validate_values(name, values, self.n_members)
-        self.member_values[name] = vals
-        if name == "epsilon":
+    def _store_member_hyper(self, name, vals):
+        if name == "epsilon":  # (the schedule's starting value)
             self.hyper["epsilon0"].copy_(torch.tensor(vals, dtype=torch.float64))
             self._one_minus_eps0.copy_(torch.tensor([1 - e for e in vals], dtype=torch.float64))
             self._eps_t = None
         else:
             self.hyper["learner"][:, DQN_NAMES.index(name)].copy_(torch.tensor(vals, dtype=torch.float64))
 
-    def member_hyper_of(self, m):
-        """{name: member m's value} for lr, discount, epsilon (the shared values without member_hyper): what the `args` of the single
-        agent that member m equals carry."""
-        m = self._member_index(m)
-        self._pull_if_dirty()
-        if self.member_values is None:
-            return {"lr": self.lr, "discount": self.discount, "epsilon": self.eps0}
-        return {k: self.member_values[k][m] for k in DQN_NAMES}
+    def _shared_hyper(self):
+        return {"lr": self.lr, "discount": self.discount, "epsilon": self.eps0}
 
     def member_state(self, m):
         """{"Q": state_dict, "target_Q": state_dict, "hyper": {lr, discount, epsilon}} of member m: the networks under
@@ -240,16 +193,7 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
         """Member m's Q-network <- a BatchedDeepQAgent.Q state dict; its target network <- target_state, or left alone; its
         hyper-parameters <- hyper ({name: value}; a population with member_hyper only), or left alone."""
         m = self._member_index(m)
-        if hyper is not None:
-            if self.hyper is None:
-                raise ValueError("this population was built without member_hyper: its hyper-parameters are shared")
-            self._pull_if_dirty()
-            for name, value in dict(hyper).items():
-                if name not in DQN_NAMES:
-                    raise ValueError("member_hyper has no %r here: the names are %s" % (name, ", ".join(DQN_NAMES)))
-                vals = list(self.member_values[name])
-                vals[m] = value
-                self.set_member_hyper(name, vals)
+        self._load_member_hyper(m, hyper)
         for dst, state in ((self.cur, q_state), (self.target, target_state)):
             if state is None:
                 continue
@@ -284,37 +228,16 @@ class BatchedDeepQPopulation(EnsembleMixin, PBTMixin):
         self.t += 1
         return self.epsilon
 
-    # -- metrics -------------------------------------------------------------------------------------------------------------------
-    def reset_member_metrics(self):
-        self.member_metrics.copy_(self._metrics_init.unsqueeze(0).expand_as(self.member_metrics))
-
-    def member_batch_metrics(self):
-        """One BatchMetrics per member from the per-member vectors (one read-back)."""
-        vecs = self.member_metrics.cpu().numpy()
-        return [BatchMetrics(v, self.env.reward_scale) for v in vecs]
-
     # -- acting --------------------------------------------------------------------------------------------------------------------
     def greedy_weights(self):
         """The stacked Q-networks in the members rollout's layout (the kernels keep w1t / w3t current)."""
         c = self.cur
         return {"w1t": self.cur_t["w1t"], "b1": c["b1"], "w2": c["w2"], "b2": c["b2"], "w3t": self.cur_t["w3t"], "b3": c["b3"]}
 
-    _ensemble_weights = greedy_weights  # (EnsembleMixin: the population's own tensors, their addresses stay)
+    _greedy_weights = _ensemble_weights = greedy_weights  # (evaluate() and EnsembleMixin: the population's own tensors, their addresses stay)
 
-    def evaluate(self, eval_timesteps):
-        """batched_default_eval (reference eval.py:8-56) for every member's Q-network, greedy: its two phases as two launches of the
-        members rollout. Returns (per-member BatchMetrics, the aggregate BatchMetrics); both metrics are reset first."""
-        env = self.env
-        env.metrics_reset()
-        self.reset_member_metrics()
-        env.reset()
-        w = self.greedy_weights()
-        if int(eval_timesteps) > 1:
-            env.policy_rollout_members(w, self.n_members, int(eval_timesteps) - 1, mode="greedy", epsilon=0.0, auto_reset=True,
-                                       member_metrics=self.member_metrics)
-        env.policy_rollout_members(w, self.n_members, int(env.info.max_iterations), mode="greedy", epsilon=0.0, auto_reset=False,
-                                   member_metrics=self.member_metrics)
-        return self.member_batch_metrics(), BatchMetrics(env.metrics(), env.reward_scale)
+    def _rollout_members(self, weights, n_steps, **kw):
+        self.env.policy_rollout_members(weights, self.n_members, n_steps, **kw)
 
     def warmup(self, n_steps, reference_state=True):
         """dqn_warmup (warmup.py:8-23) for every env of every member: the env-level streamed random rollout, as

@@ -364,18 +364,32 @@ class BatchedGridworldEnv:
             actions = actions.contiguous()
         return self._check(actions, "actions", numel=self.n_envs, dtypes=("uint8",), contiguous=False)
 
-    def _weights_arg(self, weights):
-        """sgk_mlp_weights from the dict of float32 device tensors w1t [cells, H], b1 [H], w2 [H, H], b2 [H], w3t [H, 4], b3 [4]."""
+    def _weights_arg(self, weights, lead=()):
+        """sgk_mlp_weights from the dict of float32 device tensors w1t [cells, H], b1 [H], w2 [H, H], b2 [H], w3t [H, 4], b3 [4]; with
+        lead = (n_members,) each stacked on a leading member axis and the struct addresses member 0 (_member_weights_arg). On the
+        per-step path of the single agents: one function, no helper calls."""
         try:
-            h = int(weights["b1"].numel())
-        except (KeyError, TypeError, AttributeError):
-            raise ValueError("weights must be a dict of float32 device tensors w1t, b1, w2, b2, w3t, b3") from None
+            h = int(weights["b1"].shape[-1]) if lead else int(weights["b1"].numel())
+        except (KeyError, TypeError, AttributeError, IndexError):
+            raise ValueError("weights must be a dict of %sfloat32 device tensors w1t, b1, w2, b2, w3t, b3" % ("stacked " if lead else "")) from None
         shapes = {"w1t": (self.n_cells, h), "b1": (h,), "w2": (h, h), "b2": (h,), "w3t": (h, 4), "b3": (4,)}
         for k, shape in shapes.items():
             if k not in weights:
                 raise ValueError("weights lack %r" % k)
-            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
-        return _lib.SgkMlpWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1t", "b1", "w2", "b2", "w3t", "b3")), h)
+            self._check(weights[k], "weights[%r]" % k, shape=lead + shape if lead else shape, dtypes=("float32",))
+        return _lib.SgkMlpWeights(*[ctypes.c_void_p(weights[k].data_ptr()) for k in shapes], h)
+
+    def _convq_weights(self, weights, n_channels, n_layers, lead=()):
+        """sgk_convq_weights from the dict of float32 device tensors in torch's layouts (see convq_act); with lead = (n_members,) each
+        stacked on a leading member axis and the struct addresses member 0 (_member_convq_weights)."""
+        C = int(n_channels)
+        shapes = {"w1": (C, 1, 3, 3), "b1": (C,), "w2": (C, C, 3, 3), "b2": (C,), "wb": (C, 1, 1, 1), "bb": (C,), "wh": (C, C, 3, 3),
+                  "bh": (C,), "wl": (4, C * self.n_cells), "bl": (4,)}
+        for k, shape in shapes.items():
+            if k not in weights:
+                raise ValueError("weights lack %r" % k)
+            self._check(weights[k], "weights[%r]" % k, shape=lead + shape if lead else shape, dtypes=("float32",))
+        return _lib.SgkConvQWeights(*[ctypes.c_void_p(weights[k].data_ptr()) for k in shapes], C, int(n_layers))
 
     def _scalar_arg(self, v, what, dtype):
         """(pointer or None, scalar): a 1-element device tensor is read by the launch itself (graph replays), a number is passed."""
@@ -659,65 +673,34 @@ class BatchedGridworldEnv:
         straight from the int8 boards. `weights`: dict of contiguous float32 device tensors w1t [cells,100], b1, w2
         [100,100], b2, w3t [100,4], b3. epsilon / draw_index: scalars or 1-element device tensors (float64 / int64)."""
         out = self._out_actions(out)
-        w = self._weights_arg(weights)
+        return self._act(self.lib.sgk_policy_act, self._weights_arg(weights), epsilon, draw_index, out, scores_out)
+
+    def _act(self, fn, w, epsilon, draw_index, out, scores_out):
+        """policy_act / convq_act after their weight struct `w` and `out` (checked): the scalars, scores_out, the launch `fn`."""
         eps_p, epsilon = self._scalar_arg(epsilon, "epsilon", "float64")
         draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
         sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(self.n_envs, 4),
                                                                          dtypes=("float32",)).data_ptr())
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_policy_act(self._h.ptr, ctypes.byref(w), float(epsilon), int(draw_index), eps_p, draw_p,
-                                           ctypes.c_void_p(out.data_ptr()), sp))
+        _lib.check(fn(self._h.ptr, ctypes.byref(w), float(epsilon), int(draw_index), eps_p, draw_p, ctypes.c_void_p(out.data_ptr()), sp))
         self._sync_lib_to_torch()
         return out
 
-    def _convq_weights(self, weights, n_channels, n_layers):
-        C = int(n_channels)
-        shapes = {"w1": (C, 1, 3, 3), "b1": (C,), "w2": (C, C, 3, 3), "b2": (C,), "wb": (C, 1, 1, 1), "bb": (C,), "wh": (C, C, 3, 3),
-                  "bh": (C,), "wl": (4, C * self.n_cells), "bl": (4,)}
-        for k, shape in shapes.items():
-            if k not in weights:
-                raise ValueError("weights lack %r" % k)
-            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
-        return _lib.SgkConvQWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1", "b1", "w2", "b2", "wb", "bb", "wh", "bh", "wl", "bl")),
-                                    C, int(n_layers))
-
-    def convq_act(self, weights, epsilon, draw_index, n_channels, n_layers=2, out=None, scores_out=None):
-        """A conv Q-body's forward on every env's board + DeepQAgent.act_explore in ONE launch (sgk_convq_act; a labelled non-parity
-        option: the reference's DeepQAgent is an MLP). `weights`: dict of contiguous float32 device tensors in torch's layouts -- w1
-        [C,1,3,3], b1, w2 [C,C,3,3], b2, wb [C,1,1,1], bb, wh [C,C,3,3], bh, wl [4, C * cells], bl. epsilon / draw_index: scalars or
-        1-element device tensors (float64 / int64)."""
-        w = self._convq_weights(weights, n_channels, n_layers)
-        out = self._out_actions(out)
-        eps_p, epsilon = self._scalar_arg(epsilon, "epsilon", "float64")
-        draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
-        sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(self.n_envs, 4),
-                                                                         dtypes=("float32",)).data_ptr())
-        self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_convq_act(self._h.ptr, ctypes.byref(w), float(epsilon), int(draw_index), eps_p, draw_p,
-                                          ctypes.c_void_p(out.data_ptr()), sp))
-        self._sync_lib_to_torch()
-        return out
-
-    def convq_sample(self, weights, draw_index, n_channels, n_layers=2, out=None, logits_out=None):
-        """PPOCNNAgent's trunk + actor forward (policy_cnn.py:66-74) on every env's board + PPOBaseAgent.act_explore
-        (Categorical(logits).sample(), policy_base.py:54-64) in ONE launch (sgk_convq_sample). `weights` as for convq_act with wh / bh
-        = actor_cnn and wl / bl = actor_linear; draw_index: scalar or 1-element int64 device tensor."""
-        w = self._convq_weights(weights, n_channels, n_layers)
-        out = self._out_actions(out)
+    def _sample(self, fn, w, draw_index, out, logits_out):
+        """policy_sample / convq_sample after their weight struct `w` and `out` (checked): draw_index, logits_out, the launch `fn`."""
         draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
         lp = None if logits_out is None else ctypes.c_void_p(self._check(logits_out, "logits_out", shape=(self.n_envs, 4),
                                                                          dtypes=("float32",)).data_ptr())
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_convq_sample(self._h.ptr, ctypes.byref(w), int(draw_index), draw_p, ctypes.c_void_p(out.data_ptr()), lp))
+        _lib.check(fn(self._h.ptr, ctypes.byref(w), int(draw_index), draw_p, ctypes.c_void_p(out.data_ptr()), lp))
         self._sync_lib_to_torch()
         return out
 
-    def convq_rollout(self, weights, n_steps, n_channels, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False, states=None,
-                      actions=None, recs=None, mask_finished=False, n_layers=2):
-        """n_steps of {conv body forward, action draw, env.step} in ONE HIP launch (sgk_convq_rollout): `weights` as for convq_sample
-        / convq_act; mode "sample" = Categorical(logits) (ppo-cnn's gather_rollout), "greedy" = epsilon-greedy with a fixed epsilon.
-        Outputs as for policy_rollout."""
-        w = self._convq_weights(weights, n_channels, n_layers)
+    def _rollout(self, fn, w, n_members, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs, mask_finished,
+                 member_metrics=None, member_epsilon=None):
+        """The four rollouts after their weight struct `w`: the mode and the optional outputs checked, then the launch `fn`.
+        n_members None: one network for every env (no member arguments); else the members' call, with member_metrics or None and, for
+        the _eps entry point, member_epsilon."""
         if mode not in ("greedy", "sample"):
             raise ValueError("mode must be 'greedy' or 'sample'")
 
@@ -727,14 +710,44 @@ class BatchedGridworldEnv:
             return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
 
         n = self.n_envs
+        args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
+                ptr(recs, (n_steps, n, 4), "recs", "int8"))
+        members = ()
+        if n_members is not None:
+            members = (n_members,)
+            args += (ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"),)
+            if member_epsilon is not None:
+                args += (ptr(member_epsilon, (n_members,), "member_epsilon", "float64"),)
         self._version += 1
         self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_convq_rollout(
-            self._h.ptr, ctypes.byref(w), {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
-            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0),
-            ptr(states, (n_steps, n, self.n_cells), "states", "int8"),
-            ptr(actions, (n_steps, n), "actions", "uint8"), ptr(recs, (n_steps, n, 4), "recs", "int8")))
+        _lib.check(fn(self._h.ptr, ctypes.byref(w), *members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
+                      (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
         self._sync_lib_to_torch()
+
+
+    def convq_act(self, weights, epsilon, draw_index, n_channels, n_layers=2, out=None, scores_out=None):
+        """A conv Q-body's forward on every env's board + DeepQAgent.act_explore in ONE launch (sgk_convq_act; a labelled non-parity
+        option: the reference's DeepQAgent is an MLP). `weights`: dict of contiguous float32 device tensors in torch's layouts -- w1
+        [C,1,3,3], b1, w2 [C,C,3,3], b2, wb [C,1,1,1], bb, wh [C,C,3,3], bh, wl [4, C * cells], bl. epsilon / draw_index: scalars or
+        1-element device tensors (float64 / int64)."""
+        w = self._convq_weights(weights, n_channels, n_layers)
+        return self._act(self.lib.sgk_convq_act, w, epsilon, draw_index, self._out_actions(out), scores_out)
+
+    def convq_sample(self, weights, draw_index, n_channels, n_layers=2, out=None, logits_out=None):
+        """PPOCNNAgent's trunk + actor forward (policy_cnn.py:66-74) on every env's board + PPOBaseAgent.act_explore
+        (Categorical(logits).sample(), policy_base.py:54-64) in ONE launch (sgk_convq_sample). `weights` as for convq_act with wh / bh
+        = actor_cnn and wl / bl = actor_linear; draw_index: scalar or 1-element int64 device tensor."""
+        w = self._convq_weights(weights, n_channels, n_layers)
+        return self._sample(self.lib.sgk_convq_sample, w, draw_index, self._out_actions(out), logits_out)
+
+    def convq_rollout(self, weights, n_steps, n_channels, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False, states=None,
+                      actions=None, recs=None, mask_finished=False, n_layers=2):
+        """n_steps of {conv body forward, action draw, env.step} in ONE HIP launch (sgk_convq_rollout): `weights` as for convq_sample
+        / convq_act; mode "sample" = Categorical(logits) (ppo-cnn's gather_rollout), "greedy" = epsilon-greedy with a fixed epsilon.
+        Outputs as for policy_rollout."""
+        w = self._convq_weights(weights, n_channels, n_layers)
+        self._rollout(self.lib.sgk_convq_rollout, w, None, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs,
+                      mask_finished)
 
     def categorical_sample(self, logits, draw_index, out=None):
         """PPOBaseAgent.act_explore for every env (reference policy_base.py:54-64): logits float32 [N, 4] -> uint8 actions
@@ -755,15 +768,7 @@ class BatchedGridworldEnv:
         """PPOMLPAgent (default topology) trunk + actor forward and the Categorical draw for every env in one HIP launch,
         straight from the int8 boards. `weights` as for policy_act (w3t / b3 = the actor head)."""
         out = self._out_actions(out)
-        w = self._weights_arg(weights)
-        draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
-        lp = None if logits_out is None else ctypes.c_void_p(self._check(logits_out, "logits_out", shape=(self.n_envs, 4),
-                                                                         dtypes=("float32",)).data_ptr())
-        self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_policy_sample(self._h.ptr, ctypes.byref(w), int(draw_index), draw_p,
-                                              ctypes.c_void_p(out.data_ptr()), lp))
-        self._sync_lib_to_torch()
-        return out
+        return self._sample(self.lib.sgk_policy_sample, self._weights_arg(weights), draw_index, out, logits_out)
 
     def policy_rollout(self, weights, n_steps, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False, states=None,
                        actions=None, recs=None, mask_finished=False):
@@ -773,23 +778,8 @@ class BatchedGridworldEnv:
         each action was chosen on), actions uint8 [n_steps, N], recs int8 [n_steps, N, 4]; with mask_finished the states /
         actions entries of an env whose episode is over are zeros (it idles when auto_reset is off)."""
         w = self._weights_arg(weights)
-        if mode not in ("greedy", "sample"):
-            raise ValueError("mode must be 'greedy' or 'sample'")
-
-        def ptr(t, shape, what, dtype):
-            if t is None:
-                return None
-            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
-
-        n = self.n_envs
-        self._version += 1
-        self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_policy_rollout(
-            self._h.ptr, ctypes.byref(w), {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
-            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0),
-            ptr(states, (n_steps, n, self.n_cells), "states", "int8"),
-            ptr(actions, (n_steps, n), "actions", "uint8"), ptr(recs, (n_steps, n, 4), "recs", "int8")))
-        self._sync_lib_to_torch()
+        self._rollout(self.lib.sgk_policy_rollout, w, None, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs,
+                      mask_finished)
 
     def ppo_epochs(self, learner):
         """All epochs of one PPO learn() call in ONE HIP launch (sgk_ppo_epochs); `learner` is a filled _lib.SgkPpoLearner
@@ -801,17 +791,7 @@ class BatchedGridworldEnv:
     def _member_weights_arg(self, weights, n_members):
         """sgk_mlp_weights addressing member 0 of float32 device tensors stacked on a leading member axis: w1t [M, cells, H], b1 [M, H],
         w2 [M, H, H], b2 [M, H], w3t [M, H, 4], b3 [M, 4]."""
-        try:
-            h = int(weights["b1"].shape[-1])
-        except (KeyError, TypeError, AttributeError, IndexError):
-            raise ValueError("weights must be a dict of stacked float32 device tensors w1t, b1, w2, b2, w3t, b3") from None
-        m = int(n_members)
-        shapes = {"w1t": (m, self.n_cells, h), "b1": (m, h), "w2": (m, h, h), "b2": (m, h), "w3t": (m, h, 4), "b3": (m, 4)}
-        for k, shape in shapes.items():
-            if k not in weights:
-                raise ValueError("weights lack %r" % k)
-            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
-        return _lib.SgkMlpWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1t", "b1", "w2", "b2", "w3t", "b3")), h)
+        return self._weights_arg(weights, (int(n_members),))
 
     def policy_rollout_members(self, weights, n_members, n_steps, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False,
                                states=None, actions=None, recs=None, mask_finished=False, member_metrics=None, member_epsilon=None):
@@ -824,47 +804,37 @@ class BatchedGridworldEnv:
         if n_members < 1 or self.n_envs % n_members:
             raise ValueError("n_envs (%d) is not a multiple of n_members (%d)" % (self.n_envs, n_members))
         w = self._member_weights_arg(weights, n_members)
-        if mode not in ("greedy", "sample"):
-            raise ValueError("mode must be 'greedy' or 'sample'")
-
-        def ptr(t, shape, what, dtype):
-            if t is None:
-                return None
-            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
-
-        n = self.n_envs
-        args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
-                ptr(recs, (n_steps, n, 4), "recs", "int8"), ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"))
-        fn = self.lib.sgk_policy_rollout_members
-        if member_epsilon is not None:
-            fn, args = self.lib.sgk_policy_rollout_members_eps, args + (ptr(member_epsilon, (n_members,), "member_epsilon", "float64"),)
-        self._version += 1
-        self._sync_torch_to_lib()
-        _lib.check(fn(
-            self._h.ptr, ctypes.byref(w), n_members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
-            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
-        self._sync_lib_to_torch()
+        fn = self.lib.sgk_policy_rollout_members if member_epsilon is None else self.lib.sgk_policy_rollout_members_eps
+        self._rollout(fn, w, n_members, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs, mask_finished,
+                      member_metrics, member_epsilon)
 
     def policy_act_members_all(self, weights, n_members, out=None, scores_out=None):
         """Every member's GREEDY action on EVERY env's current board in ONE HIP launch (sgk_policy_act_members_all): the cross product
         the ensemble votes over. `weights` stacked on a leading member axis (see _member_weights_arg); returns uint8 [n_members, N]
         (`out` when given), row m what policy_act(member m's slices, epsilon=0.0) gives, bit for bit; scores_out: float32
         [n_members, N, 4] on this device that receives the scores, or None. The envs are not touched."""
+        n_members, w, out, sp = self._members_all_args(n_members, lambda m: self._member_weights_arg(weights, m), out, scores_out)
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_policy_act_members_all(self._h.ptr, ctypes.byref(w), n_members, ctypes.c_void_p(out.data_ptr()), sp))
+        self._sync_lib_to_torch()
+        return out
+
+    def _members_all_args(self, n_members, weights_struct, out, scores_out):
+        """What the two *_act_members_all calls check, in their order: n_members in 1 .. MEMBERS_MAX, the weight struct
+        (weights_struct(n_members) builds it), `out` uint8 [n_members, N] (made when None) and scores_out float32 [n_members, N, 4] or
+        None. Returns (n_members, the struct, out, scores_out's pointer or None)."""
         import torch
 
         n_members = int(n_members)
         if not 1 <= n_members <= _lib.MEMBERS_MAX:
             raise ValueError("n_members must be in 1..%d, not %d" % (_lib.MEMBERS_MAX, n_members))
-        w = self._member_weights_arg(weights, n_members)
+        w = weights_struct(n_members)
         if out is None:
             out = torch.empty((n_members, self.n_envs), dtype=torch.uint8, device="cuda:%d" % self.device)
         self._check(out, "out", shape=(n_members, self.n_envs), dtypes=("uint8",))
         sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(n_members, self.n_envs, 4),
                                                                          dtypes=("float32",)).data_ptr())
-        self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_policy_act_members_all(self._h.ptr, ctypes.byref(w), n_members, ctypes.c_void_p(out.data_ptr()), sp))
-        self._sync_lib_to_torch()
-        return out
+        return n_members, w, out, sp
 
     def members_vote(self, member_actions, members=None, out=None, votes_out=None, dissent=None):
         """The plurality vote per env over member_actions, uint8 [M, N] on this device (what policy_act_members_all returns), in ONE
@@ -932,46 +902,50 @@ class BatchedGridworldEnv:
         _lib.SgkPpoLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None.
         member_hyper: float64 [n_members, 4] on this device, rows (lr, clipping, critic_coeff, entropy_bonus) that replace the learner's
         four (sgk_ppo_epochs_members_hyper), or None."""
+        self._learn_members(self.lib.sgk_ppo_epochs_members, self.lib.sgk_ppo_epochs_members_hyper, learner, n_members, member_keys,
+                            member_hyper, 4)
+
+    def _learn_members(self, fn, fn_hyper, learner, n_members, member_keys, member_hyper, n_fields, *extra):
+        """A members learner call: member_keys int64 [n_members] or None and member_hyper float64 [n_members, n_fields] or None
+        checked, then `fn` (shared hyper-parameters) or `fn_hyper` (member_hyper's rows); `extra` follows the keys in both."""
+        n_members = int(n_members)
         kp = None
         if member_keys is not None:
-            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
-        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 4)
+            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(n_members,), dtypes=("int64",)).data_ptr())
+        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, n_fields)
         self._sync_torch_to_lib()
         if hp is None:
-            _lib.check(self.lib.sgk_ppo_epochs_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp))
+            _lib.check(fn(self._h.ptr, ctypes.byref(learner), n_members, kp, *extra))
         else:
-            _lib.check(self.lib.sgk_ppo_epochs_members_hyper(self._h.ptr, ctypes.byref(learner), int(n_members), kp, hp))
+            _lib.check(fn_hyper(self._h.ptr, ctypes.byref(learner), n_members, kp, *extra, hp))
         self._sync_lib_to_torch()
+
+    def _workspace_bytes(self, fn, *sizes):
+        """What a *_workspace_bytes entry point answers for `sizes`; SgkError when it refuses them (a negative answer)."""
+        nbytes = fn(self._h.ptr, *(int(s) for s in sizes))
+        if nbytes < 0:
+            _lib.check(_lib.ERR_INVALID)
+        return int(nbytes)
 
     def dqn_members_workspace_bytes(self, n_hidden, n_members):
         """Bytes of device workspace sgk_dqn_sgd_step_members needs on this level for n_members members of n_hidden units; SgkError
         for a shape without a kernel."""
-        nbytes = self.lib.sgk_dqn_members_workspace_bytes(self._h.ptr, int(n_hidden), int(n_members))
-        if nbytes < 0:
-            _lib.check(_lib.ERR_INVALID)
-        return int(nbytes)
+        return self._workspace_bytes(self.lib.sgk_dqn_members_workspace_bytes, n_hidden, n_members)
 
     def dqn_sgd_step_members(self, learner, n_members, member_keys=None, workspace=None, member_hyper=None):
         """One DeepQAgent.learn() of n_members independent agents in two HIP launches (sgk_dqn_sgd_step_members); `learner` is a filled
         _lib.SgkDqnLearner addressing member 0 of the stacked tensors, member_keys a uint64-as-int64 [n_members] device tensor or None,
         workspace a uint8 device tensor of dqn_members_workspace_bytes() bytes that the caller keeps alive. member_hyper: float64
         [n_members, 2] on this device, rows (lr, discount) that replace the learner's two (sgk_dqn_sgd_step_members_hyper), or None."""
-        kp = wp = None
-        if member_keys is not None:
-            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(int(n_members),), dtypes=("int64",)).data_ptr())
+        wp = None
         if workspace is not None:
             key = (int(learner.n_hidden), int(n_members))
             need = self._dqn_ws_bytes.get(key)
             if need is None:
                 need = self._dqn_ws_bytes[key] = self.dqn_members_workspace_bytes(*key)
             wp = ctypes.c_void_p(self._check(workspace, "workspace", numel=need, dtypes=("uint8",)).data_ptr())
-        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 2)
-        self._sync_torch_to_lib()
-        if hp is None:
-            _lib.check(self.lib.sgk_dqn_sgd_step_members(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp))
-        else:
-            _lib.check(self.lib.sgk_dqn_sgd_step_members_hyper(self._h.ptr, ctypes.byref(learner), int(n_members), kp, wp, hp))
-        self._sync_lib_to_torch()
+        self._learn_members(self.lib.sgk_dqn_sgd_step_members, self.lib.sgk_dqn_sgd_step_members_hyper, learner, n_members, member_keys,
+                            member_hyper, 2, wp)
 
     def ppo_cnn_epochs(self, learner):
         """All epochs of one PPOCNNAgent learn() call on the device, three HIP launches per epoch (sgk_ppo_cnn_epochs); `learner` is a
@@ -982,23 +956,12 @@ class BatchedGridworldEnv:
 
     def ppo_cnn_workspace_bytes(self, n_channels, batch):
         """Bytes of device workspace sgk_ppo_cnn_epochs needs on this level with n_channels and batch rows; SgkError when unsupported."""
-        nbytes = self.lib.sgk_ppo_cnn_workspace_bytes(self._h.ptr, int(n_channels), int(batch))
-        if nbytes < 0:
-            _lib.check(_lib.ERR_INVALID)
-        return int(nbytes)
+        return self._workspace_bytes(self.lib.sgk_ppo_cnn_workspace_bytes, n_channels, batch)
 
     def _member_convq_weights(self, weights, n_members, n_channels, n_layers):
         """sgk_convq_weights addressing member 0 of float32 device tensors stacked on a leading member axis: w1 [M, C, 1, 3, 3], b1
         [M, C], w2 [M, C, C, 3, 3], b2, wb [M, C, 1, 1, 1], bb, wh [M, C, C, 3, 3], bh, wl [M, 4, C * cells], bl [M, 4]."""
-        C, m = int(n_channels), int(n_members)
-        shapes = {"w1": (m, C, 1, 3, 3), "b1": (m, C), "w2": (m, C, C, 3, 3), "b2": (m, C), "wb": (m, C, 1, 1, 1), "bb": (m, C),
-                  "wh": (m, C, C, 3, 3), "bh": (m, C), "wl": (m, 4, C * self.n_cells), "bl": (m, 4)}
-        for k, shape in shapes.items():
-            if k not in weights:
-                raise ValueError("weights lack %r" % k)
-            self._check(weights[k], "weights[%r]" % k, shape=shape, dtypes=("float32",))
-        return _lib.SgkConvQWeights(*(ctypes.c_void_p(weights[k].data_ptr()) for k in ("w1", "b1", "w2", "b2", "wb", "bb", "wh", "bh", "wl", "bl")),
-                                    C, int(n_layers))
+        return self._convq_weights(weights, n_channels, n_layers, (int(n_members),))
 
     def convq_rollout_members(self, weights, n_members, n_steps, n_channels, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False,
                               states=None, actions=None, recs=None, mask_finished=False, member_metrics=None, n_layers=2):
@@ -1010,23 +973,8 @@ class BatchedGridworldEnv:
         if n_members < 1 or self.n_envs % n_members:
             raise ValueError("n_envs (%d) is not a multiple of n_members (%d)" % (self.n_envs, n_members))
         w = self._member_convq_weights(weights, n_members, n_channels, n_layers)
-        if mode not in ("greedy", "sample"):
-            raise ValueError("mode must be 'greedy' or 'sample'")
-
-        def ptr(t, shape, what, dtype):
-            if t is None:
-                return None
-            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
-
-        n = self.n_envs
-        args = (ptr(states, (n_steps, n, self.n_cells), "states", "int8"), ptr(actions, (n_steps, n), "actions", "uint8"),
-                ptr(recs, (n_steps, n, 4), "recs", "int8"), ptr(member_metrics, (n_members, _lib.METRICS_LEN), "member_metrics", "int64"))
-        self._version += 1
-        self._sync_torch_to_lib()
-        _lib.check(self.lib.sgk_convq_rollout_members(
-            self._h.ptr, ctypes.byref(w), n_members, {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
-            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0), *args))
-        self._sync_lib_to_torch()
+        self._rollout(self.lib.sgk_convq_rollout_members, w, n_members, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions,
+                      recs, mask_finished, member_metrics)
 
     def convq_act_members_all(self, weights, n_members, n_channels, n_layers=2, out=None, scores_out=None):
         """Every member's GREEDY action on EVERY env's current board in ONE HIP launch (sgk_convq_act_members_all): the conv bodies'
@@ -1034,17 +982,8 @@ class BatchedGridworldEnv:
         _member_convq_weights; wh / bh / wl / bl = the actor head); returns uint8 [n_members, N] (`out` when given), row m what
         convq_act(member m's slices, epsilon=0.0) gives, bit for bit; scores_out: float32 [n_members, N, 4] on this device that
         receives the four outputs, or None. The envs are not touched."""
-        import torch
-
-        n_members = int(n_members)
-        if not 1 <= n_members <= _lib.MEMBERS_MAX:
-            raise ValueError("n_members must be in 1..%d, not %d" % (_lib.MEMBERS_MAX, n_members))
-        w = self._member_convq_weights(weights, n_members, n_channels, n_layers)
-        if out is None:
-            out = torch.empty((n_members, self.n_envs), dtype=torch.uint8, device="cuda:%d" % self.device)
-        self._check(out, "out", shape=(n_members, self.n_envs), dtypes=("uint8",))
-        sp = None if scores_out is None else ctypes.c_void_p(self._check(scores_out, "scores_out", shape=(n_members, self.n_envs, 4),
-                                                                         dtypes=("float32",)).data_ptr())
+        n_members, w, out, sp = self._members_all_args(n_members, lambda m: self._member_convq_weights(weights, m, n_channels, n_layers),
+                                                       out, scores_out)
         o = _lib.SgkMembersActOut(ctypes.c_void_p(out.data_ptr()), sp)
         self._sync_torch_to_lib()
         _lib.check(self.lib.sgk_convq_act_members_all(self._h.ptr, ctypes.byref(w), n_members, ctypes.byref(o)))
@@ -1054,10 +993,7 @@ class BatchedGridworldEnv:
     def ppo_cnn_members_workspace_bytes(self, n_channels, batch, n_members):
         """Bytes of device workspace sgk_ppo_cnn_epochs_members needs on this level for n_members members with n_channels and batch
         rows; SgkError when unsupported."""
-        nbytes = self.lib.sgk_ppo_cnn_members_workspace_bytes(self._h.ptr, int(n_channels), int(batch), int(n_members))
-        if nbytes < 0:
-            _lib.check(_lib.ERR_INVALID)
-        return int(nbytes)
+        return self._workspace_bytes(self.lib.sgk_ppo_cnn_members_workspace_bytes, n_channels, batch, n_members)
 
     def ppo_cnn_epochs_members(self, learner, n_members, member_keys=None, member_hyper=None):
         """One learn() call of n_members independent PPOCNNAgents, three HIP launches per epoch (sgk_ppo_cnn_epochs_members); `learner`
@@ -1067,16 +1003,8 @@ class BatchedGridworldEnv:
         n_members = int(n_members)
         if n_members < 1 or int(learner.n_trajectories) % n_members:
             raise ValueError("n_trajectories (%d) is not a multiple of n_members (%d)" % (int(learner.n_trajectories), n_members))
-        kp = None
-        if member_keys is not None:
-            kp = ctypes.c_void_p(self._check(member_keys, "member_keys", shape=(n_members,), dtypes=("int64",)).data_ptr())
-        hp = None if member_hyper is None else self._member_hyper_arg(member_hyper, n_members, 4)
-        self._sync_torch_to_lib()
-        if hp is None:
-            _lib.check(self.lib.sgk_ppo_cnn_epochs_members(self._h.ptr, ctypes.byref(learner), n_members, kp))
-        else:
-            _lib.check(self.lib.sgk_ppo_cnn_epochs_members_hyper(self._h.ptr, ctypes.byref(learner), n_members, kp, hp))
-        self._sync_lib_to_torch()
+        self._learn_members(self.lib.sgk_ppo_cnn_epochs_members, self.lib.sgk_ppo_cnn_epochs_members_hyper, learner, n_members, member_keys,
+                            member_hyper, 4)
 
     def discounted_returns(self, rewards, discount, lengths=None, out=None):
         """PPOBaseAgent.get_discounted_returns (reference policy_base.py:179-186) for a batch: rewards float32

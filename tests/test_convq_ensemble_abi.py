@@ -174,7 +174,10 @@ def test_the_wrapper_refuses_a_wrong_tensor_with_a_value_error():
     # (the checks are raises, not asserts: `python -O` leaves them in)
     import inspect
 
-    body = inspect.getsource(BatchedGridworldEnv.convq_act_members_all) + inspect.getsource(BatchedGridworldEnv._member_convq_weights)
+    body = "".join(inspect.getsource(getattr(BatchedGridworldEnv, name)) for name in (  # the two and every helper they delegate to
+        "convq_act_members_all", "_member_convq_weights", "_members_all_args", "_convq_weights", "_check"))
+    for mark in ("n_members must be in", "weights lack", "has shape"):  # (the checks the cases above met are in what was read)
+        assert mark in body
     assert "assert " not in body
 
 
