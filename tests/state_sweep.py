@@ -22,8 +22,9 @@ COIN_ENVS = ("AbsentSupervisor-v0", "SafeInterruptibility-v0")
 SWEPT = ("BoatRace-v0", "IslandNavigation-v0", "SideEffectsSokoban-v0", "DistributionalShift-v0", "AbsentSupervisor-v0",
          "SafeInterruptibility-v0", "ConveyorBelt-v0")
 # WhiskyGold replaces actions by its own draws once the whisky is drunk, TomatoWatering and FriendFoe draw every step: the same
-# machinery with scripts built on env index 0, no coverage requirement (what they reach is logged). TomatoWatering's requirement is
-# stated in events and planned per env around its drying schedule: tests/tomato_sweep.py
+# machinery with scripts built on env index 0, no coverage requirement HERE (what they reach is logged). Their requirements are stated in
+# events and planned per env around that env's own draws, which never depend on the actions: TomatoWatering's in tests/tomato_sweep.py,
+# WhiskyGold's in tests/whisky_sweep.py, FriendFoe's in tests/foe_sweep.py (the latter two: test_draw_sweeps_cpu.py, test_gpu_draw_sweeps.py)
 UNSWEPT = ("WhiskyGold-v0", "TomatoWatering-v0", "FriendFoe-v0")
 DEPTH_CAP = 98  # the episode limit is 100 steps; the deepest state (ConveyorBelt) is found at depth 19
 SEED = 5
@@ -105,8 +106,12 @@ def state_index_of_board(name):
         H, W = O.shape(name)
         env = types.SimpleNamespace(name=name, n_cells=H * W, W=W)
         index = {}
+        # WhiskyGold's (sober, on the whisky's cell) is no state -- arriving there drinks --, and it renders the board of (drunk, on that
+        # cell), which is one: that board belongs to the drunk index
+        no_state = {int(O.EnvBatch(name, 1).field("box_cell")[0])} if name == "WhiskyGold-v0" else set()
         for si in range(n_states(name)):
-            index.setdefault(_board_of_state(env, si).tobytes(), si)
+            if si not in no_state:
+                index.setdefault(_board_of_state(env, si).tobytes(), si)
         _INDEX_CACHE[name] = index
     return _INDEX_CACHE[name]
 
@@ -300,6 +305,113 @@ def trace(name, seed, n, actions=None, policy=None, schedule=True, T=None, env_b
     tr.metrics = m.copy()
     tr.metrics[O.M_STEPS] = n * T
     tr.orc = orc  # the batch in its final state (FriendFoe's estimates, last_performance(i))
+    return tr
+
+
+_AUX_OFFSET = []
+
+
+def foe_estimates(orc):
+    """FriendFoe's six float64 estimates of every env of an oracle batch as bit patterns, uint64 [n, 6], in one numpy view of the
+    batch's records instead of n calls (65 637 envs x every step). Where the six doubles lie in a record is FOUND, not assumed: the
+    bytes of foe_policy() behind one played episode occur exactly once in that env's record; a test holds the view to foe_policy()."""
+    if not _AUX_OFFSET:
+        e = O.EnvBatch("FriendFoe-v0", 1, seed=1)
+        for a in (0, 0, 0, 2, 0, 0, 0, 3, 0, 0, 0, 3, 0, 0, 0, 2):  # four shortest episodes: up, up, up, left / right (auto-reset by hand)
+            if e.step(0, a)[2]:
+                e.reset(0)
+        want = e.foe_policy(0).tobytes()
+        assert len({x for x in np.frombuffer(want, dtype=np.float64).tolist()}) >= 3
+        raw = e.buf.raw[: e.rec]
+        at = raw.find(want)
+        assert at >= 0 and at % 8 == 0 and raw.find(want, at + 1) < 0
+        _AUX_OFFSET.append(at)
+    at = _AUX_OFFSET[0]
+    raw = np.frombuffer(orc.buf, dtype=np.uint8, count=orc.rec * orc.n).reshape(orc.n, orc.rec)
+    return np.ascontiguousarray(raw[:, at:at + 48]).view(np.uint64).reshape(orc.n, 6)
+
+
+PRE_FIELDS = ("agent_cell", "box_cell", "game_over", "frame", "n_episodes")
+
+
+def trace_phases(name, seed, n, phases, env_begin=0, pre=True):
+    """The oracle's record of ONE batch that plays `phases` one behind the other: a list of (payload, schedule) with payload = an
+    action script uint8 [T_p, n] or a memoryless policy int8 [n, n_states], and schedule = one of trace()'s kinds per step of the
+    phase ("auto" / "none" / "reset"); (None, "reset_all") between two phases resets the whole batch and the metrics. A Trace over all
+    steps as trace() makes it, and besides:
+      aux0 / aux   uint64 [n, 6] / [T, n, 6]: FriendFoe's estimates as bit patterns before the first and behind EVERY step
+      before       {field of PRE_FIELDS, "n_resets": int32 [T, n]} and boards_before: the state every step starts from, and how often
+                   the env has been reset by then
+      pre          {field of PRE_FIELDS: int32 [T, n]} and boards_pre: the state a step leaves BEFORE the reset that may follow it
+                   (`pre`: every "auto" step is played as the step and the resets of the finished envs, which is what auto-reset means;
+                   pre=False plays it in one call of the oracle -- a batch of 65 637 envs -- and leaves these four out)
+      phase_end    the index of every phase's last step; metrics_at: the metrics behind it (M_STEPS as the library counts them)."""
+    orc = O.EnvBatch(name, n, seed=seed, env_begin=env_begin)
+    foe = name == "FriendFoe-v0"
+    T = sum(len(sch) for payload, sch in phases if payload is not None)
+    m, t_metrics = O.metrics_new(), 0
+    tr = Trace()
+    tr.name, tr.n, tr.T, tr.schedule = name, n, T, [k for payload, sch in phases if payload is not None for k in sch]
+    tr.boards0, f0 = orc.export()
+    tr.fields0 = {k: v.copy() for k, v in f0.items()}
+    tr.recs = np.zeros((T, n, 4), dtype=np.int8)
+    tr.boards = np.zeros((T, n, orc.H * orc.W), dtype=np.int8)
+    tr.boards_pre = np.zeros_like(tr.boards) if pre else None
+    tr.fields = {k: np.zeros((T, n), dtype=np.int32) for k in FIELDS}
+    tr.pre = {k: np.zeros((T, n), dtype=np.int32) for k in PRE_FIELDS} if pre else None
+    tr.before = {k: np.zeros((T, n), dtype=np.int32) for k in PRE_FIELDS + ("n_resets",)} if pre else None
+    n_resets = np.ones(n, dtype=np.int32)  # counted here, reset by reset (the create-time reset is number 1): what keys the draws
+    tr.boards_before = np.zeros_like(tr.boards) if pre else None
+    tr.actions = np.zeros((T, n), dtype=np.uint8)
+    tr.aux0 = foe_estimates(orc) if foe else np.zeros((n, 6), dtype=np.uint64)
+    tr.aux = np.zeros((T, n, 6), dtype=np.uint64)
+    tr.phase_end, tr.metrics_at = [], []
+    boards, f = tr.boards0, tr.fields0
+    t = 0
+    for payload, sch in phases:
+        if payload is None:  # (None, "reset_all"): the whole batch is reset and the metrics start again -- what evaluate() does first
+            assert sch == "reset_all"
+            orc.reset()
+            n_resets += 1
+            m, t_metrics = O.metrics_new(), t
+            boards, f = orc.export()
+            continue
+        script = payload.dtype == np.uint8
+        assert payload.shape == ((len(sch), n) if script else (n, n_states(name))), payload.shape
+        for j, kind in enumerate(sch):
+            acts = np.ascontiguousarray(payload[j]) if script else policy_actions(name, boards, payload)
+            tr.actions[t] = acts
+            if pre:
+                tr.boards_before[t] = boards
+                for k in PRE_FIELDS:
+                    tr.before[k][t] = f[k]
+                tr.before["n_resets"][t] = n_resets
+            tr.recs[t] = orc.rollout(1, seed=seed, env_begin=env_begin, t_begin=t, auto_reset=kind == "auto" and not pre,
+                                     actions=acts[None], metrics=m)
+            if pre:
+                tr.boards_pre[t], fp = orc.export()
+                for k in PRE_FIELDS:
+                    tr.pre[k][t] = fp[k]
+                if kind != "none":
+                    for i in np.nonzero(fp["game_over"])[0]:
+                        orc.reset(int(i))
+                        n_resets[i] += 1
+            elif kind == "reset":
+                for i in np.nonzero(orc.field("game_over"))[0]:
+                    orc.reset(int(i))
+            boards, f = orc.export()
+            tr.boards[t] = boards
+            for k in FIELDS:
+                tr.fields[k][t] = f[k]
+            if foe:
+                tr.aux[t] = foe_estimates(orc)
+            t += 1
+        tr.phase_end.append(t - 1)
+        mm = m.copy()
+        mm[O.M_STEPS] = n * (t - t_metrics)
+        tr.metrics_at.append(mm)
+    tr.metrics = tr.metrics_at[-1].copy()
+    tr.orc = orc
     return tr
 
 

@@ -13,7 +13,9 @@ sgk_step_host through the step server in batches of at most 64 envs; step_store 
 tabular-Q agents acting greedily on private scripted policies (epsilon 0, lr 0): act + env.step, step, learn_steps, rollout
 lds / hbm, evaluate lds / hbm, the tables' bytes unchanged behind every learning call.
 
-WhiskyGold, TomatoWatering and FriendFoe draw by themselves: they run the action-script paths without a coverage requirement.
+WhiskyGold, TomatoWatering and FriendFoe draw by themselves: they run the action-script paths without a coverage requirement HERE.
+Theirs is stated in events and planned per env around that env's own draws: test_gpu_tomato_sweep.py (TomatoWatering) and
+test_gpu_draw_sweeps.py (WhiskyGold and FriendFoe, the time limit and FriendFoe's estimates behind every step included).
 
 "Every scriptable path" is no wider than this list. Not swept: the grid-stride instantiations above 65 536 envs of anything but
 env.step on BoatRace (step_store's STORE form and tabq_step_kernel among them); tabq act + env.step on a compact handle (it runs
@@ -202,7 +204,8 @@ def test_step_store_and_reset_done_store_execute_every_pair(name, layout, cheat,
         _same_bytes(succ[sl].cpu().numpy(), tr.boards_pre[t], where + " successors ring")
         _same_bytes(ract[sl].cpu().numpy(), tr.recs[t, :, 3].astype(np.uint8) if cheat else tr.actions[t], where + " actions ring")
         _same_bytes(rrew[sl].cpu().numpy(), tr.recs[t, :, 1 if cheat else 0], where + " rewards ring")
-        # (no episode of a sweep reaches the time limit: an episode that ends here ends in a terminal state)
+        # (no episode of THIS sweep reaches the time limit: an episode that ends here ends in a terminal state; the time-limit plans of
+        # test_gpu_draw_sweeps.py end episodes the other way)
         _same_bytes(rterm[sl].cpu().numpy(), tr.recs[t, :, 2].astype(np.uint8), where + " terminals ring")
         env.reset_done_store(states, t + 1, slice_dev=slice_dev)
         _same_bytes(states[(base + t + 1) % ring].cpu().numpy(), tr.boards[t], where + " states ring")

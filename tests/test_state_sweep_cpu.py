@@ -4,7 +4,7 @@ the action form and in the policy form, and the product's host code (sgk_debug_h
 bookkeeping on the packed state word) follows the same trace state word by state word. test_gpu_state_sweep.py holds every
 scriptable device path to these traces step by step, which is how the coverage reaches the board writers and state carriers of
 the device. WhiskyGold, TomatoWatering and FriendFoe draw by themselves: they run the same machinery with scripts built on env
-index 0 and carry no coverage requirement.
+index 0 and carry no coverage requirement here (theirs: test_tomato_sweep_cpu.py, test_draw_sweeps_cpu.py).
 
 `python tests/test_state_sweep_cpu.py` writes profiles/state_sweep/coverage.log: per level the reachable states and pairs, what
 the sweeps execute, and for comparison what the oracle's replay of the suite's own walks executes."""
