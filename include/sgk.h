@@ -578,6 +578,47 @@ SGK_API int sgk_convq_rollout_members(sgk_env *h, const sgk_convq_weights *w, in
                                       uint64_t draw_index0, int32_t n_steps, uint32_t flags, int8_t *states_out_dev,
                                       uint8_t *actions_out_dev, sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev);
 
+/* ---- the same body on the observation of a transition env: two input channels, [previous board, board] ------------------------------
+ * The reference's TransitionBoatRace observes [last board, board], and [board, board] at a reset; its PPOCRMDPAgent / PPOCNNAgent is
+ * then built with two input channels. These three calls are sgk_convq_act / _sample / _rollout for that body:
+ *   `w` is sgk_convq_weights with w1 [C][2][3][3] and wb [C][2][1][1] (torch's layouts: channel 0 = the previous board, 1 = the current
+ *   one); every other tensor, n_channels and n_layers as above. The struct's layout is unchanged: the caller vouches for the two sizes.
+ *   `tr` carries EVERYTHING writable -- the previous boards and all outputs -- so that no entry point here has a non-const pointer
+ *   parameter (tests/test_guard_arena_cpu.py lists those of the whole header):
+ *     prev_boards_dev       int8 [n_envs][n_cells], dense. act / sample: read only, or NULL = every env's previous board is its current
+ *                           one. rollout: required; read at entry unless fresh != 0, WRITTEN at exit with the previous-board channel of
+ *                           the observation the NEXT action would be chosen on (the board before the last step; the current board for
+ *                           an env the last step reset), so that the next call -- of any of the three -- continues the trajectory.
+ *     prev_states_out_dev   rollout only: int8 [n_steps][n_envs][n_cells] or NULL -- channel 0 of the observation each action was chosen
+ *                           on, beside states_out_dev's channel 1; zeros where states_out_dev holds zeros (SGK_F_MASK_FINISHED).
+ *     fresh                 rollout only: != 0 -- no env has stepped since its reset: previous := current at entry.
+ *     actions_out_dev       act / sample: uint8 [n_envs], required. rollout: uint8 [n_steps][n_envs] or NULL.
+ *     scores_out_dev        act / sample only: float32 [n_envs][4] (the scores / logits), 16-byte aligned, or NULL.
+ *     states_out_dev, recs_out_dev   rollout only: sgk_convq_rollout's optional outputs.
+ *   An env that SGK_F_AUTO_RESET resets inside the rollout acts next on [board, board]. An env that idles (its episode is over, no
+ *   auto-reset) still moves on: its previous board becomes its current one.
+ * Draws, RNG keys, flags, metrics, optional outputs and the boards materialised at the end are those of the one-channel calls; like
+ * them these allocate nothing, never synchronise the host and can be captured in a graph. Kernels exist for the 5 x 5 board (BoatRace)
+ * and n_channels in {4, 5, 8}; there is no member form. SGK_ERR_INVALID with a message and nothing launched for a NULL `tr`, a NULL
+ * prev_boards_dev in the rollout, another board shape, and whatever the one-channel call refuses.
+ * Guard bands: tests/test_gpu_transition_body.py carves every pointer field of `tr` from tests/guard_arena.py's arena;
+ * tests/test_transition_cpu.py requires every pointer field of the struct to name one such test. */
+typedef struct sgk_convq_transition {
+  int8_t *prev_boards_dev;
+  int8_t *prev_states_out_dev;
+  int32_t fresh;
+  int8_t *states_out_dev;
+  uint8_t *actions_out_dev;
+  sgk_step_rec *recs_out_dev;
+  float *scores_out_dev;
+} sgk_convq_transition;
+SGK_API int sgk_convq_act_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, double epsilon, uint64_t draw_index,
+                                const double *epsilon_dev, const uint64_t *draw_index_dev);
+SGK_API int sgk_convq_sample_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, uint64_t draw_index,
+                                   const uint64_t *draw_index_dev);
+SGK_API int sgk_convq_rollout_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, int32_t mode, double epsilon,
+                                    uint64_t draw_index0, int32_t n_steps, uint32_t flags);
+
 /* The two halves of the replay add FUSED into the launches around them (round 6; a lockstep step of dqn_learn -- learn.py:29-58 -- is
  * then sgk_policy_act, sgk_step_store, sgk_dqn_sgd_step, sgk_reset_done_store: four calls instead of six -- or three, with the last two
  * as sgk_dqn_sgd_step_reset_store):

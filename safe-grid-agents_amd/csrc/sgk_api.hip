@@ -988,6 +988,62 @@ int sgk_convq_sample(sgk_env *h, const sgk_convq_weights *w, uint64_t draw_index
   return convq_launch(h, w, 1, 0.0, draw_index, nullptr, draw_index_dev, actions_out_dev, logits_out_dev);
 } SGK_CATCH_STATUS
 
+// ---- the two-channel body (a transition env's [previous board, board]) ----
+static int convq_trans_ok(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, const char *fn) {
+  // (the arguments first: these refusals need no handle and no device)
+  if (int rc = convq_weights_ok(w)) return rc;
+  if (!tr) return fail(SGK_ERR_INVALID, "%s: the transition descriptor is NULL", fn);
+  SGK_CHECK_HANDLE(h);
+  if (!sgk::convq_trans_board_has_kernel(h->sh.rules_host.height, h->sh.rules_host.width) || h->sh.env_id != SGK_BOAT_RACE)
+    return fail(SGK_ERR_INVALID, "%s: the two-channel conv body is built for BoatRace's 5 x 5 board (this env: level %d, %d x %d)", fn,
+                (int)h->sh.env_id, h->sh.rules_host.height, h->sh.rules_host.width);
+  return SGK_OK;
+}
+
+static int convq_trans_launch(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, int mode, double epsilon,
+                              uint64_t draw_index, const double *epsilon_dev, const uint64_t *draw_index_dev, const char *fn) {
+  if (int rc = convq_trans_ok(h, w, tr, fn)) return rc;
+  if (!tr->actions_out_dev) return fail(SGK_ERR_INVALID, "%s: actions_out_dev is NULL", fn);
+  if (tr->scores_out_dev && ((uintptr_t)tr->scores_out_dev & 15u))
+    return fail(SGK_ERR_INVALID, "%s: the scores / logits output must be 16-byte aligned", fn);
+  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  SGK_HIP(sgk::launch_convq_act_trans(h->sh, cw, w->n_channels, mode, tr->prev_boards_dev, tr->actions_out_dev, tr->scores_out_dev, epsilon,
+                                      draw_index, epsilon_dev, draw_index_dev, h->stream));
+  return SGK_OK;
+}
+
+int sgk_convq_act_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, double epsilon, uint64_t draw_index,
+                        const double *epsilon_dev, const uint64_t *draw_index_dev) try {
+  return convq_trans_launch(h, w, tr, 0, epsilon, draw_index, epsilon_dev, draw_index_dev, "sgk_convq_act_trans");
+} SGK_CATCH_STATUS
+
+int sgk_convq_sample_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, uint64_t draw_index,
+                           const uint64_t *draw_index_dev) try {
+  return convq_trans_launch(h, w, tr, 1, 0.0, draw_index, nullptr, draw_index_dev, "sgk_convq_sample_trans");
+} SGK_CATCH_STATUS
+
+int sgk_convq_rollout_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_convq_transition *tr, int32_t mode, double epsilon,
+                            uint64_t draw_index0, int32_t n_steps, uint32_t flags) try {
+  if (int rc = convq_trans_ok(h, w, tr, "sgk_convq_rollout_trans")) return rc;
+  if (!tr->prev_boards_dev)
+    return fail(SGK_ERR_INVALID, "sgk_convq_rollout_trans: prev_boards_dev is NULL (the rollout leaves the next observation's previous boards there)");
+  if (mode != 0 && mode != 1) return fail(SGK_ERR_INVALID, "mode must be 0 (epsilon-greedy) or 1 (categorical)");
+  if (n_steps < 0) return fail(SGK_ERR_INVALID, "n_steps < 0");
+  if (flags & ~(uint32_t)(SGK_F_AUTO_RESET | SGK_F_MASK_FINISHED))
+    return fail(SGK_ERR_INVALID, "only SGK_F_AUTO_RESET and SGK_F_MASK_FINISHED are meaningful here");
+  if (n_steps == 0) return SGK_OK;
+  sgk::Shard &s = h->sh;
+  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  SGK_HIP(sgk::launch_convq_rollout_trans(s, cw, w->n_channels, mode, epsilon, draw_index0, n_steps, flags, tr->prev_boards_dev, tr->fresh,
+                                          tr->states_out_dev, tr->prev_states_out_dev, tr->actions_out_dev,
+                                          reinterpret_cast<uint32_t *>(tr->recs_out_dev), h->stream));
+  SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
+  s.lockstep_t += (uint64_t)n_steps;
+  h->t_dev_stale = true;
+  h->steps_issued += s.n * n_steps;
+  return SGK_OK;
+} SGK_CATCH_STATUS
+
 int sgk_convq_act_members_all(sgk_env *h, const sgk_convq_weights *w, int32_t n_members, const sgk_members_act_out *out) try {
   // (the arguments first: the refusals need no handle and no device)
   if (int rc = convq_weights_ok(w)) return rc;

@@ -32,13 +32,16 @@ __device__ __forceinline__ void cq_static_for(F &&f) {
   }
 }
 
-template <int HH, int WW, int C>
+// CI: input planes. 1 = the board; 2 = the observation of a transition env, [previous board, board] (sgk_convq_*_trans): the inputs are
+// planes 0 .. CI - 1, and everything behind them sits CI - 1 planes higher.
+template <int HH, int WW, int C, int CI_ = 1>
 struct ConvQGeom {
+  static constexpr int CI = CI_;
   static constexpr int NC = HH * WW;                     // cells
   static constexpr int PW = WW + 1;                      // row pitch: W cells + the zero column shared with the next row
   static constexpr int SE = HH * PW;                     // slots of one env (interior rows, border column included)
   static constexpr int PL = (HH + 2) * PW + 1;           // floats per plane: a zero row above and below, one leading zero
-  static constexpr int PLANES = 1 + 2 * C;               // x | h1 (later: the linear head's per-slot products) | trunk
+  static constexpr int PLANES = CI + 2 * C;              // x | h1 (later: the linear head's per-slot products) | trunk
   static constexpr int GPW = CQ_GPW, GROUPS = 4 * GPW, SLOTS = 64 * GROUPS;  // 64-slot groups per pass: GPW per wave
   static constexpr int ENVS = SLOTS / SE;                // envs per pass
   static constexpr int ENV_F0 = PLANES * PL;
@@ -46,7 +49,7 @@ struct ConvQGeom {
   static constexpr int CR = (C % 4 == 1) ? 1 : 0;        // a lone fifth channel: scalar-weight FMAs instead of a 1/4-full MFMA tile
   static constexpr int MT = (C + 3) / 4 - CR;            // 4-channel row tiles on the MFMA
   static constexpr int CM = CR ? 4 * MT : C;             // channels on the MFMA
-  static constexpr int K1 = 9, K2 = 9 * C, KC2 = (K2 + 15) / 16;
+  static constexpr int K1 = 9 * CI, KC1 = (K1 + 15) / 16, K2 = 9 * C, KC2 = (K2 + 15) / 16;
   static constexpr int NF = C * NC;                      // linear inputs
   static constexpr int WLR = 4 * C;                      // the linear weights of one slot: [action][channel]
   // (the activations first: their LDS address is then the lane's own base register alone, and a row's constant offset fits the 8-bit
@@ -57,6 +60,8 @@ struct ConvQGeom {
   static constexpr size_t lds_bytes = sizeof(float) * (size_t)(O_WL + SE * WLR);
   static constexpr int NB = (ENVS * NC + CQ_WG - 1) / CQ_WG;  // board bytes per lane and pass
   static_assert(ENVS >= 1 && 4 * PL <= C * PL && SE <= PL, "convq geometry");
+  static_assert(CI == 1 || CI == 2, "one board, or a transition's two");
+  static_assert(ENV_F % 32 == SE % 32 && ENV_F >= PLANES * PL, "env pitch");
 };
 
 typedef float cq_f4 __attribute__((ext_vector_type(4)));
@@ -139,7 +144,7 @@ __device__ __forceinline__ float cq_channel(const cq_f4 (&acc)[G::MT], float rac
 // what a lane keeps for the whole launch: the three convolutions' A operands and its slots
 template <class G>
 struct CqLane {
-  float a1[G::MT][1], a2[G::MT][G::KC2], ah[G::MT][G::KC2];
+  float a1[G::MT][G::KC1], a2[G::MT][G::KC2], ah[G::MT][G::KC2];
   int base[G::GPW], wlrow[G::GPW];
   int pbase[G::GPW][G::NPG];  // base + the first plane of every group of four
   bool interior[G::GPW];
@@ -155,7 +160,11 @@ __device__ __forceinline__ void cq_setup(CqLane<G> &L, float *WL, float *act, co
 #pragma unroll
     for (int m = 0; m < G::MT; ++m) {
       const int c = 4 * m + i;
-      L.a1[m][0] = (c < G::CM && kk < G::K1) ? w1r[c * 9 + kk] : 0.0f;
+#pragma unroll
+      for (int q = 0; q < G::KC1; ++q) {
+        const int k = 16 * q + kk;
+        L.a1[m][q] = (c < G::CM && k < G::K1) ? w1r[c * G::K1 + k] : 0.0f;  // [c][ci][dy][dx] flattened = c * 9 CI + k
+      }
 #pragma unroll
       for (int q = 0; q < G::KC2; ++q) {
         const int k = 16 * q + kk;
@@ -190,8 +199,8 @@ __device__ __forceinline__ void cq_setup(CqLane<G> &L, float *WL, float *act, co
   }
 }
 
-// the network on the boards in plane 0: three convolutions, the linear head's per-slot products left in planes 1 .. 4. Starts behind a
-// barrier that made plane 0 visible, ends with the barrier that makes the products visible. hz: always 0, but not to the compiler (the
+// the network on the boards in plane 0 (CI = 2: planes 0 and 1): three convolutions, the linear head's per-slot products left in planes
+// CI .. CI + 3. Starts behind a barrier that made the input planes visible, ends with the barrier that makes the products visible. hz: always 0, but not to the compiler (the
 // fifth channel's scalar weights are then loaded per pass into scalar registers instead of being hoisted into ~100 vector registers
 // for the whole launch, which halves the occupancy).
 template <class G, int C>
@@ -199,40 +208,49 @@ __device__ __forceinline__ void cq_network(const CqLane<G> &L, float *act, const
                                            const float *__restrict__ b1r, const float *__restrict__ w2r, const float *__restrict__ b2r,
                                            const float *__restrict__ wbr, const float *__restrict__ bbr, const float *__restrict__ whr,
                                            const float *__restrict__ bhr) {
-  // ---- conv3x3 1 -> C, ReLU: planes 1 .. C (border slots are never written: they stay zero) ----
+  // ---- conv3x3 CI -> C, ReLU: planes CI .. CI + C - 1 (border slots are never written: they stay zero) ----
   {
     cq_f4 acc[G::GPW][G::MT] = {};
     float racc[G::GPW] = {};
-    cq_taps<G, G::K1, 1, 0>(act, L.pbase, L.a1, w1r + G::CM * G::K1 + hz, acc, racc);
+    cq_taps<G, G::K1, G::KC1, 0>(act, L.pbase, L.a1, w1r + G::CM * G::K1 + hz, acc, racc);
 #pragma unroll
     for (int j = 0; j < G::GPW; ++j)
       if (L.interior[j]) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) act[L.base[j] + (1 + c) * G::PL + G::CENTRE] = fmaxf(cq_channel<G>(acc[j], racc[j], c) + b1r[c + hz], 0.0f);
+        for (int c = 0; c < C; ++c) act[L.base[j] + (G::CI + c) * G::PL + G::CENTRE] = fmaxf(cq_channel<G>(acc[j], racc[j], c) + b1r[c + hz], 0.0f);
       }
   }
   __syncthreads();
-  // ---- conv3x3 C -> C, ReLU, + the 1 x 1 bottleneck of the board: planes C + 1 .. 2 C (the trunk) ----
+  // ---- conv3x3 C -> C, ReLU, + the 1 x 1 bottleneck of the input planes: planes CI + C .. CI + 2 C - 1 (the trunk) ----
   {
     cq_f4 acc[G::GPW][G::MT] = {};
     float racc[G::GPW] = {};
-    cq_taps<G, G::K2, G::KC2, 1>(act, L.pbase, L.a2, w2r + G::CM * G::K2 + hz, acc, racc);
+    cq_taps<G, G::K2, G::KC2, G::CI>(act, L.pbase, L.a2, w2r + G::CM * G::K2 + hz, acc, racc);
 #pragma unroll
     for (int j = 0; j < G::GPW; ++j)
       if (L.interior[j]) {
         const float xin = act[L.base[j] + G::CENTRE];
+        if constexpr (G::CI == 1) {
 #pragma unroll
-        for (int c = 0; c < C; ++c)
-          act[L.base[j] + (1 + C + c) * G::PL + G::CENTRE] =
-              fmaxf(cq_channel<G>(acc[j], racc[j], c) + b2r[c + hz], 0.0f) + fmaf(wbr[c + hz], xin, bbr[c + hz]);
+          for (int c = 0; c < C; ++c)
+            act[L.base[j] + (1 + C + c) * G::PL + G::CENTRE] =
+                fmaxf(cq_channel<G>(acc[j], racc[j], c) + b2r[c + hz], 0.0f) + fmaf(wbr[c + hz], xin, bbr[c + hz]);
+        } else {  // wb [C][2][1][1]: the previous board (plane 0, xin), then the current one (plane 1, xin1)
+          const float xin1 = act[L.base[j] + G::PL + G::CENTRE];
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+            act[L.base[j] + (G::CI + C + c) * G::PL + G::CENTRE] =
+                fmaxf(cq_channel<G>(acc[j], racc[j], c) + b2r[c + hz], 0.0f) + fmaf(wbr[2 * c + 1 + hz], xin1, fmaf(wbr[2 * c + hz], xin, bbr[c + hz]));
+        }
       }
   }
   __syncthreads();
-  // ---- head conv3x3 C -> C, ReLU, times this slot's rows of the linear layer: four per-slot products into planes 1 .. 4 ----
+  // ---- head conv3x3 C -> C, ReLU, times this slot's rows of the linear layer: four per-slot products into planes CI .. CI + 3 ----
+  // (never an input plane: in the acting kernel the other waves write the next pass's boards while wave 0 still sums the products)
   {
     cq_f4 acc[G::GPW][G::MT] = {};
     float racc[G::GPW] = {};
-    cq_taps<G, G::K2, G::KC2, 1 + C>(act, L.pbase, L.ah, whr + G::CM * G::K2 + hz, acc, racc);
+    cq_taps<G, G::K2, G::KC2, G::CI + C>(act, L.pbase, L.ah, whr + G::CM * G::K2 + hz, acc, racc);
 #pragma unroll
     for (int j = 0; j < G::GPW; ++j)
       if (L.interior[j]) {
@@ -254,7 +272,7 @@ __device__ __forceinline__ void cq_network(const CqLane<G> &L, float *act, const
           float sacc = 0.0f;
 #pragma unroll
           for (int c = 0; c < C; ++c) sacc = fmaf(hv[c], wr[a * C + c], sacc);
-          act[L.base[j] + (1 + a) * G::PL + G::CENTRE] = sacc;
+          act[L.base[j] + (G::CI + a) * G::PL + G::CENTRE] = sacc;
         }
       }
   }
@@ -268,7 +286,7 @@ __device__ __forceinline__ void cq_outputs(const float *act, const float *__rest
   const int lane = threadIdx.x & 63;
   const bool live = idx < G::ENVS * 4;
   const int e = live ? idx >> 2 : 0, a = idx & 3;
-  const float *p = act + e * G::ENV_F + (1 + a) * G::PL + G::CENTRE;
+  const float *p = act + e * G::ENV_F + (G::CI + a) * G::PL + G::CENTRE;
   float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
   constexpr int SE3 = G::SE / 3;
 #pragma unroll 2

@@ -213,6 +213,117 @@ hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int 
   return hipGetLastError();
 }
 
+// sgk_convq_act_trans / sgk_convq_sample_trans: the same forward on the observation of a transition env, [previous board, board]
+// (ConvQGeom's CI = 2: w1 [C][2][3][3], wb [C][2][1][1]). convq_act_kernel's pass loop with one difference: a lane requests its bytes of
+// BOTH boards for the next pass -- the current one from the env's own boards (`pitch`), the previous one from `prev`, the caller's dense
+// int8 [n][NC] array; null = the current board twice (no env has stepped since its reset) -- and writes them to planes 1 and 0. A
+// kernel of its own, so that convq_act_kernel stays the instruction stream it was. No member form.
+template <int HH, int WW, int C>
+__global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_trans_kernel(
+    const int8_t *__restrict__ boards, const int8_t *__restrict__ prev, int pitch, const float *__restrict__ w1r, const float *__restrict__ b1r,
+    const float *__restrict__ w2r, const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr,
+    const float *__restrict__ whr, const float *__restrict__ bhr, const float *__restrict__ wlr, const float *__restrict__ blr,
+    uint8_t *__restrict__ actions, float *__restrict__ scores_out, int64_t n, int mode, double eps, uint64_t seed, uint64_t env_base,
+    uint64_t draw, const double *__restrict__ eps_ptr, const uint64_t *__restrict__ draw_ptr) {
+  typedef ConvQGeom<HH, WW, C, 2> G;
+  extern __shared__ __attribute__((aligned(16))) unsigned char convq_smem[];
+  float *Lf = reinterpret_cast<float *>(convq_smem);
+  float *WL = Lf + G::O_WL, *act = Lf + G::O_ACT;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (eps_ptr) eps = *eps_ptr;
+  if (draw_ptr) draw = *draw_ptr;
+  CqLane<G> L;
+  cq_setup<G, WW, C>(L, WL, act, w1r, w2r, whr, wlr);
+  // ---- this lane's board bytes of a pass: element i = t + CQ_WG * u = (env e, cell pos) ----
+  int b_lds[G::NB], b_env[G::NB], b_goff[G::NB];
+  int8_t cur[G::NB], prv[G::NB];
+#pragma unroll
+  for (int u = 0; u < G::NB; ++u) {
+    const int i = t + CQ_WG * u;
+    const bool live = i < G::ENVS * G::NC;
+    const int e = live ? i / G::NC : 0, pos = live ? i - e * G::NC : 0;
+    const int y = pos / WW, x = pos - y * WW;
+    b_env[u] = live ? e : 0x7fffffff;
+    b_goff[u] = e * pitch + pos;
+    b_lds[u] = e * G::ENV_F + G::CENTRE + y * G::PW + x;
+    cur[u] = prv[u] = 0;
+  }
+  const int64_t n_pass = (n + G::ENVS - 1) / G::ENVS;
+  auto request_boards = [&](int64_t pass) {
+    const int8_t *src = boards + pass * G::ENVS * (int64_t)pitch;  // (uniform)
+    const int8_t *psrc = prev ? prev + pass * G::ENVS * (int64_t)G::NC : nullptr;
+    const int64_t left = n - pass * G::ENVS;
+    const int lim = left < G::ENVS ? (int)left : G::ENVS;
+#pragma unroll
+    for (int u = 0; u < G::NB; ++u) {
+      cur[u] = b_env[u] < lim ? src[b_goff[u]] : (int8_t)0;
+      prv[u] = !psrc ? cur[u] : b_env[u] < lim ? psrc[t + CQ_WG * u] : (int8_t)0;  // (e < lim: element i lies inside [n][NC])
+    }
+  };
+  if ((int64_t)blockIdx.x < n_pass) request_boards(blockIdx.x);
+  __syncthreads();
+  for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+    const int64_t env0 = pass * G::ENVS;
+    const int hz = (int)(pass >> 44);  // (always 0: see cq_network)
+    // ---- previous -> plane 0, current -> plane 1 (float); the next pass's bytes requested ----
+#pragma unroll
+    for (int u = 0; u < G::NB; ++u)
+      if (b_env[u] < G::ENVS) {
+        act[b_lds[u]] = (float)prv[u];
+        act[b_lds[u] + G::PL] = (float)cur[u];
+      }
+    if (pass + gridDim.x < n_pass) request_boards(pass + gridDim.x);
+    __syncthreads();
+    cq_network<G, C>(L, act, WL, hz, w1r, b1r, w2r, b2r, wbr, bbr, whr, bhr);
+    if (wave == 0) {
+      constexpr int NIT = (G::ENVS * 4 + 63) / 64;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int idx = it * 64 + lane;
+        float q0, q1, q2, q3;
+        cq_outputs<G>(act, blr, idx, q0, q1, q2, q3);
+        const int64_t env = env0 + (idx >> 2);
+        if (idx < G::ENVS * 4 && (idx & 3) == 0 && env < n) {
+          actions[env] = (uint8_t)(mode == 0 ? pick_action<0>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps)
+                                             : pick_action<1>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps));
+          if (scores_out) *reinterpret_cast<float4 *>(scores_out + 4 * env) = make_float4(q0, q1, q2, q3);
+        }
+      }
+    }
+    // (the next pass writes planes 0 and 1 first and passes a barrier before the planes behind them are written again: wave 0 sums
+    // the products in planes 2 .. 5 meanwhile, which is why they are not left in plane 1 ..)
+  }
+}
+
+// the two-plane kernel exists for the 5 x 5 board (BoatRace, the level TransitionBoatRace wraps); another level is a dispatch line
+hipError_t launch_convq_act_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, const int8_t *prev_boards, uint8_t *actions,
+                                  float *scores, double eps, uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
+  (void)hipGetLastError();
+#define SGK_CONVQ_TRANS_LAUNCH(HV, WV, CV)                                                                                 \
+  do {                                                                                                                     \
+    typedef ConvQGeom<HV, WV, CV, 2> G2;                                                                                   \
+    constexpr size_t lds = G2::lds_bytes;                                                                                  \
+    static_assert(lds <= 160u * 1024u, "convq LDS plan");                                                                 \
+    const int64_t n_pass = (sh.n + G2::ENVS - 1) / G2::ENVS;                                                               \
+    hipError_t ae = allow_dynamic_lds<convq_act_trans_kernel<HV, WV, CV>>(sh.device, (int)lds);                            \
+    if (ae != hipSuccess) return ae;                                                                                       \
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                 \
+    const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
+    convq_act_trans_kernel<HV, WV, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(                                              \
+        sh.boards, prev_boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl, actions, scores, sh.n, mode, eps, sh.seed, \
+        sh.env_base, draw, eps_dev, draw_dev);                                                                             \
+  } while (0)
+  if (!convq_trans_board_has_kernel(sh.rules_host.height, sh.rules_host.width)) return hipErrorInvalidValue;
+  if (n_channels == 5) SGK_CONVQ_TRANS_LAUNCH(5, 5, 5);
+  else if (n_channels == 4) SGK_CONVQ_TRANS_LAUNCH(5, 5, 4);
+  else if (n_channels == 8) SGK_CONVQ_TRANS_LAUNCH(5, 5, 8);
+  else return hipErrorInvalidValue;
+#undef SGK_CONVQ_TRANS_LAUNCH
+  return hipGetLastError();
+}
+
+bool convq_trans_board_has_kernel(int height, int width) { return height == 5 && width == 5; }
+
 bool convq_board_has_kernel(int height, int width) {
   const int boards[][2] = {{5, 5}, {6, 5}, {6, 6}, {6, 8}, {7, 7}, {7, 8}, {7, 9}};
   for (const auto &b : boards)

@@ -121,6 +121,15 @@ bool convq_board_has_kernel(int height, int width);  // the board shapes launch_
 hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0, int32_t n_steps,
                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
                                 int n_members = 0, int64_t *member_metrics = nullptr);
+// the same two launches on the observation of a transition env, [previous board, board] (sgk_convq_*_trans): w.w1 is [C][2][3][3] and
+// w.wb [C][2][1][1]; prev_boards: dense int8 [n][n_cells] (acting: read, null = the current board twice; rollout: read at entry unless
+// `fresh`, written at exit, never null); prev_states_out: channel 0 beside states_out's channel 1, or null
+hipError_t launch_convq_act_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, const int8_t *prev_boards, uint8_t *actions,
+                                  float *scores, double eps, uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st);
+hipError_t launch_convq_rollout_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0,
+                                      int32_t n_steps, uint32_t flags, int8_t *prev_boards, int fresh, int8_t *states_out,
+                                      int8_t *prev_states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st);
+bool convq_trans_board_has_kernel(int height, int width);  // the board shapes the two launches above dispatch
 // one member's hyper-parameters in device memory: the layouts of sgk_ppo_member_hyper / sgk_dqn_member_hyper (sgk.h; sgk_api.hip checks)
 struct PpoMemberHyper {
   double lr, clipping, critic_coeff, entropy_bonus;

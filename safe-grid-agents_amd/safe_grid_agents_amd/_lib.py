@@ -116,6 +116,13 @@ class SgkMembersActOut(ctypes.Structure):
     _fields_ = [("member_actions_dev", ctypes.c_void_p), ("member_scores_dev", ctypes.c_void_p)]
 
 
+class SgkConvQTransition(ctypes.Structure):
+    """sgk_convq_transition: the previous boards and every output of sgk_convq_act_trans / _sample_trans / _rollout_trans."""
+    _fields_ = [("prev_boards_dev", ctypes.c_void_p), ("prev_states_out_dev", ctypes.c_void_p), ("fresh", ctypes.c_int32),
+                ("states_out_dev", ctypes.c_void_p), ("actions_out_dev", ctypes.c_void_p), ("recs_out_dev", ctypes.c_void_p),
+                ("scores_out_dev", ctypes.c_void_p)]
+
+
 class SgkTabqHashVotes(ctypes.Structure):
     """sgk_tabq_hash_votes: every output of sgk_tabq_hash_consensus and its workspace."""
     _fields_ = [("keys", ctypes.c_void_p), ("votes", ctypes.c_void_p), ("voters", ctypes.c_void_p), ("count", ctypes.c_void_p),
@@ -214,6 +221,11 @@ _SIGNATURES = {
                                          ctypes.c_uint32, _V, _V, _V]),
     "sgk_convq_rollout_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                                  ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, _V, _V, _V, _V]),
+    "sgk_convq_act_trans": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.POINTER(SgkConvQTransition), ctypes.c_double,
+                                           ctypes.c_uint64, _V, _V]),
+    "sgk_convq_sample_trans": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.POINTER(SgkConvQTransition), ctypes.c_uint64, _V]),
+    "sgk_convq_rollout_trans": (ctypes.c_int, [_V, ctypes.POINTER(SgkConvQWeights), ctypes.POINTER(SgkConvQTransition), ctypes.c_int32,
+                                               ctypes.c_double, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32]),
     "sgk_step_store": (ctypes.c_int, [_V, _V, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int64, _V, ctypes.c_int32, _V, _V, _V, _V]),
     "sgk_reset_done_store": (ctypes.c_int, [_V, ctypes.c_uint32, ctypes.c_int64, _V, ctypes.c_int32, _V]),
     "sgk_ppo_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner)]),

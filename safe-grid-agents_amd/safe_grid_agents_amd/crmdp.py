@@ -10,9 +10,10 @@ learns from a lower Lipschitz bound in place of their reward. The detection runs
                          read back as dictionaries keyed by (prev cell, cur cell).
   BatchedPPOCRMDPAgent   BatchedPPOAgent(body="cnn") on a batched BoatRace env: the existing gather, then keys -> filter -> the existing
                          returns scan on the filtered rewards, all on the device. ONE memory; env order is the reference's rollout order
-                         (-r N). A labelled NON-parity: the detector sees transitions (board before, board after), the POLICY sees the
-                         current board only, as batched `trans-boat ppo-cnn` does today (the 2-channel body exists in the single-env
-                         agent only).
+                         (-r N). transitions=True is the PARITY form: the policy acts on [previous board, board] through the two-channel
+                         fused kernels (sgk_convq_rollout_trans) and reproduces the reference's own `-r N trans-boat ppo-crmdp` run
+                         (tests/golden/batched_ppo_crmdp_transboat.npz). The default stays a labelled NON-parity: the detector sees
+                         transitions (board before, board after), the POLICY the current board only.
 
 Only the metric of TransitionBoatRace exists (d_trans_boat); the reference's other three levels live in its fork of
 ai-safety-gridworlds alone, and another level is the reference's KeyError. The reference's _purge_memory is never entered on this
@@ -220,8 +221,10 @@ class BatchedPPOCRMDPAgent(BatchedPPOAgent):
     reference's rollout order with -r N), and sgk_discounted_returns scans the filtered rewards. Nothing leaves the device but, once per
     iteration, three integers (stats()).
 
-    NON-parity, labelled: the detector sees transitions, the policy does not -- it acts on the current board (1 channel), as batched
-    `trans-boat ppo-cnn` does today. The single-env PPOCRMDPAgent is the parity path.
+    transitions=True (passed on to BatchedPPOAgent) is the PARITY path: the policy is the reference's two-channel PPOCNNAgent acting on
+    [previous board, board] ([board, board] at a reset), gathered by sgk_convq_rollout_trans; it reproduces the reference's own run
+    (tests/test_gpu_transition_golden.py). The default (transitions=False) is NON-parity, labelled: the detector sees transitions, the
+    policy does not -- it acts on the current board (1 channel). The single-env PPOCRMDPAgent is the parity path for one env.
 
     on_unbounded: "raise" (default) -- stats() raises RuntimeError naming the first trajectory with a corrupt state that has no bound
     (the reference's None and its crash); "keep" -- such steps keep their reward and are only counted."""

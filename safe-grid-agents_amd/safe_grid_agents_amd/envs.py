@@ -379,17 +379,49 @@ class BatchedGridworldEnv:
             self._check(weights[k], "weights[%r]" % k, shape=lead + shape if lead else shape, dtypes=("float32",))
         return _lib.SgkMlpWeights(*[ctypes.c_void_p(weights[k].data_ptr()) for k in shapes], h)
 
-    def _convq_weights(self, weights, n_channels, n_layers, lead=()):
+    def _convq_weights(self, weights, n_channels, n_layers, lead=(), in_channels=1):
         """sgk_convq_weights from the dict of float32 device tensors in torch's layouts (see convq_act); with lead = (n_members,) each
-        stacked on a leading member axis and the struct addresses member 0 (_member_convq_weights)."""
-        C = int(n_channels)
-        shapes = {"w1": (C, 1, 3, 3), "b1": (C,), "w2": (C, C, 3, 3), "b2": (C,), "wb": (C, 1, 1, 1), "bb": (C,), "wh": (C, C, 3, 3),
+        stacked on a leading member axis and the struct addresses member 0 (_member_convq_weights). in_channels = 2: the body of a
+        transition env (w1 [C, 2, 3, 3], wb [C, 2, 1, 1]; the struct itself does not say which)."""
+        C, ci = int(n_channels), int(in_channels)
+        shapes = {"w1": (C, ci, 3, 3), "b1": (C,), "w2": (C, C, 3, 3), "b2": (C,), "wb": (C, ci, 1, 1), "bb": (C,), "wh": (C, C, 3, 3),
                   "bh": (C,), "wl": (4, C * self.n_cells), "bl": (4,)}
         for k, shape in shapes.items():
             if k not in weights:
                 raise ValueError("weights lack %r" % k)
             self._check(weights[k], "weights[%r]" % k, shape=lead + shape if lead else shape, dtypes=("float32",))
         return _lib.SgkConvQWeights(*[ctypes.c_void_p(weights[k].data_ptr()) for k in shapes], C, int(n_layers))
+
+    def _convq_in_channels(self, weights, prev_boards, n_channels, n_layers):
+        """1 or 2: the input channels `weights` are built for (w1 [C, in, 3, 3]). Two = the observation of a transition env, [previous
+        board, board]: the call goes to the _trans entry point. prev_boards with a one-channel body is an error."""
+        w1 = weights.get("w1") if hasattr(weights, "get") else None
+        ci = int(w1.shape[1]) if w1 is not None and getattr(w1, "ndim", 0) == 4 else 1
+        if ci not in (1, 2):
+            raise ValueError("weights['w1'] has %d input channels: the fused conv body takes 1 (the board) or 2 (previous board, board)" % ci)
+        if ci == 1 and prev_boards is not None:
+            raise ValueError("prev_boards given, but weights['w1'] has one input channel: a transition body's w1 is [C, 2, 3, 3]")
+        if ci == 2:  # what sgk_convq_*_trans would refuse, said before anything is launched
+            if int(self.info.env_id) != ENV_IDS["BoatRace-v0"] or (self.H, self.W) != (5, 5):
+                raise ValueError("the two-channel conv body is built for BoatRace's 5 x 5 board, not level %d (%d x %d)"
+                                 % (int(self.info.env_id), self.H, self.W))
+            if int(n_channels) not in (4, 5, 8) or int(n_layers) != 2:
+                raise ValueError("the two-channel conv body is built for n_channels in (4, 5, 8) and n_layers == 2, not %d and %d"
+                                 % (int(n_channels), int(n_layers)))
+        return ci
+
+    def _transition_arg(self, prev_boards, actions, scores=None, prev_states=None, fresh=False, states=None, recs=None, n_steps=None):
+        """sgk_convq_transition from checked tensors (None = NULL)."""
+        def ptr(t, shape, what, dtype):
+            if t is None:
+                return None
+            return ctypes.c_void_p(self._check(t, what, shape=shape, dtypes=(dtype,)).data_ptr())
+
+        n, nc = self.n_envs, self.n_cells
+        traj = (n,) if n_steps is None else (n_steps, n)
+        return _lib.SgkConvQTransition(ptr(prev_boards, (n, nc), "prev_boards", "int8"), ptr(prev_states, traj + (nc,), "prev_states", "int8"),
+                                       1 if fresh else 0, ptr(states, traj + (nc,), "states", "int8"), ptr(actions, traj, "actions", "uint8"),
+                                       ptr(recs, traj + (4,), "recs", "int8"), ptr(scores, (n, 4), "scores_out", "float32"))
 
     def _scalar_arg(self, v, what, dtype):
         """(pointer or None, scalar): a 1-element device tensor is read by the launch itself (graph replays), a number is passed."""
@@ -725,29 +757,69 @@ class BatchedGridworldEnv:
         self._sync_lib_to_torch()
 
 
-    def convq_act(self, weights, epsilon, draw_index, n_channels, n_layers=2, out=None, scores_out=None):
+    def convq_act(self, weights, epsilon, draw_index, n_channels, n_layers=2, out=None, scores_out=None, prev_boards=None):
         """A conv Q-body's forward on every env's board + DeepQAgent.act_explore in ONE launch (sgk_convq_act; a labelled non-parity
         option: the reference's DeepQAgent is an MLP). `weights`: dict of contiguous float32 device tensors in torch's layouts -- w1
         [C,1,3,3], b1, w2 [C,C,3,3], b2, wb [C,1,1,1], bb, wh [C,C,3,3], bh, wl [4, C * cells], bl. epsilon / draw_index: scalars or
-        1-element device tensors (float64 / int64)."""
-        w = self._convq_weights(weights, n_channels, n_layers)
-        return self._act(self.lib.sgk_convq_act, w, epsilon, draw_index, self._out_actions(out), scores_out)
+        1-element device tensors (float64 / int64).
+        A body with TWO input channels (w1 [C,2,3,3], wb [C,2,1,1]: a transition env's [previous board, board]) goes to
+        sgk_convq_act_trans: prev_boards is int8 [N, cells] on this device, None = every env's previous board is its current one."""
+        ci = self._convq_in_channels(weights, prev_boards, n_channels, n_layers)
+        w = self._convq_weights(weights, n_channels, n_layers, in_channels=ci)
+        out = self._out_actions(out)
+        if ci == 1:
+            return self._act(self.lib.sgk_convq_act, w, epsilon, draw_index, out, scores_out)
+        tr = self._transition_arg(prev_boards, out, scores=scores_out)
+        eps_p, epsilon = self._scalar_arg(epsilon, "epsilon", "float64")
+        draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_convq_act_trans(self._h.ptr, ctypes.byref(w), ctypes.byref(tr), float(epsilon), int(draw_index), eps_p, draw_p))
+        self._sync_lib_to_torch()
+        return out
 
-    def convq_sample(self, weights, draw_index, n_channels, n_layers=2, out=None, logits_out=None):
+    def convq_sample(self, weights, draw_index, n_channels, n_layers=2, out=None, logits_out=None, prev_boards=None):
         """PPOCNNAgent's trunk + actor forward (policy_cnn.py:66-74) on every env's board + PPOBaseAgent.act_explore
         (Categorical(logits).sample(), policy_base.py:54-64) in ONE launch (sgk_convq_sample). `weights` as for convq_act with wh / bh
-        = actor_cnn and wl / bl = actor_linear; draw_index: scalar or 1-element int64 device tensor."""
-        w = self._convq_weights(weights, n_channels, n_layers)
-        return self._sample(self.lib.sgk_convq_sample, w, draw_index, self._out_actions(out), logits_out)
+        = actor_cnn and wl / bl = actor_linear; draw_index: scalar or 1-element int64 device tensor. A two-channel body and prev_boards
+        as for convq_act (sgk_convq_sample_trans)."""
+        ci = self._convq_in_channels(weights, prev_boards, n_channels, n_layers)
+        w = self._convq_weights(weights, n_channels, n_layers, in_channels=ci)
+        out = self._out_actions(out)
+        if ci == 1:
+            return self._sample(self.lib.sgk_convq_sample, w, draw_index, out, logits_out)
+        tr = self._transition_arg(prev_boards, out, scores=logits_out)
+        draw_p, draw_index = self._scalar_arg(draw_index, "draw_index", "int64")
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_convq_sample_trans(self._h.ptr, ctypes.byref(w), ctypes.byref(tr), int(draw_index), draw_p))
+        self._sync_lib_to_torch()
+        return out
 
     def convq_rollout(self, weights, n_steps, n_channels, mode="sample", epsilon=0.0, draw_index0=0, auto_reset=False, states=None,
-                      actions=None, recs=None, mask_finished=False, n_layers=2):
+                      actions=None, recs=None, mask_finished=False, n_layers=2, prev_boards=None, prev_states=None, fresh=False):
         """n_steps of {conv body forward, action draw, env.step} in ONE HIP launch (sgk_convq_rollout): `weights` as for convq_sample
         / convq_act; mode "sample" = Categorical(logits) (ppo-cnn's gather_rollout), "greedy" = epsilon-greedy with a fixed epsilon.
-        Outputs as for policy_rollout."""
-        w = self._convq_weights(weights, n_channels, n_layers)
-        self._rollout(self.lib.sgk_convq_rollout, w, None, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs,
-                      mask_finished)
+        Outputs as for policy_rollout.
+        A two-channel body (see convq_act) goes to sgk_convq_rollout_trans and needs prev_boards, int8 [N, cells]: read at entry unless
+        fresh (no env has stepped since its reset), and left holding the previous boards of the observation the next action would be
+        chosen on. prev_states: int8 [n_steps, N, cells] or None, channel 0 beside `states`' channel 1."""
+        ci = self._convq_in_channels(weights, prev_boards, n_channels, n_layers)
+        w = self._convq_weights(weights, n_channels, n_layers, in_channels=ci)
+        if ci == 1:
+            if prev_states is not None or fresh:
+                raise ValueError("prev_states / fresh belong to a two-channel body (weights['w1'] is [C, 2, 3, 3]) and its prev_boards")
+            return self._rollout(self.lib.sgk_convq_rollout, w, None, n_steps, mode, epsilon, draw_index0, auto_reset, states, actions, recs,
+                                 mask_finished)
+        if mode not in ("greedy", "sample"):
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        if prev_boards is None:
+            raise ValueError("a two-channel body's rollout needs prev_boards (int8 [N, cells]): it leaves the next observation's previous boards there")
+        tr = self._transition_arg(prev_boards, actions, prev_states=prev_states, fresh=fresh, states=states, recs=recs, n_steps=int(n_steps))
+        self._version += 1
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_convq_rollout_trans(
+            self._h.ptr, ctypes.byref(w), ctypes.byref(tr), {"greedy": 0, "sample": 1}[mode], float(epsilon), int(draw_index0), int(n_steps),
+            (_lib.F_AUTO_RESET if auto_reset else 0) | (_lib.F_MASK_FINISHED if mask_finished else 0)))
+        self._sync_lib_to_torch()
 
     def categorical_sample(self, logits, draw_index, out=None):
         """PPOBaseAgent.act_explore for every env (reference policy_base.py:54-64): logits float32 [N, 4] -> uint8 actions
@@ -1316,6 +1388,7 @@ def make(name, n_envs=None, **kwargs):
         return GridworldEnv(name, **kwargs)
     if name in TRANSITION_ENVS:
         # batched: the same kernels; the two-board observation is what a 2-slice trajectory ring holds
-        # (rollout_random_stream(..., boards=ring) with ring.shape[0] == 2: slice k % 2 = board after step k)
+        # (rollout_random_stream(..., boards=ring) with ring.shape[0] == 2: slice k % 2 = board after step k); a conv policy sees it as
+        # [previous board, board] through convq_act / convq_sample / convq_rollout with prev_boards (BatchedPPOAgent(transitions=True))
         name = TRANSITION_ENVS[name]
     return BatchedGridworldEnv(name, n_envs, **kwargs)

@@ -188,8 +188,13 @@ def batched_default_eval(agent, env, eval_timesteps):
     weights = agent.greedy_weights() if hasattr(agent, "greedy_weights") else None
     if weights is not None:  # fused policy: each phase is one sgk_policy_rollout / sgk_convq_rollout launch (auto-reset == step + reset_done)
         if "wh" in weights:  # a conv body
+            prev = getattr(agent, "prev_boards", None) if getattr(agent, "transitions", False) else None
+            fresh = [prev is not None]  # a transition body: behind the reset above previous = current; the second phase carries on
+
             def rollout(k, auto_reset):
-                env.convq_rollout(weights, k, int(weights["b1"].numel()), mode="greedy", epsilon=0.0, auto_reset=auto_reset)
+                kw = {} if prev is None else {"prev_boards": prev, "fresh": fresh[0]}
+                env.convq_rollout(weights, k, int(weights["b1"].numel()), mode="greedy", epsilon=0.0, auto_reset=auto_reset, **kw)
+                fresh[0] = False
         else:
             def rollout(k, auto_reset):
                 env.policy_rollout(weights, k, mode="greedy", epsilon=0.0, auto_reset=auto_reset)
@@ -197,6 +202,8 @@ def batched_default_eval(agent, env, eval_timesteps):
             rollout(int(eval_timesteps) - 1, True)
         rollout(int(env.info.max_iterations), False)
         return BatchMetrics(env.metrics(), env.reward_scale)
+    if getattr(agent, "transitions", False):  # (as gather_rollout: the fused rollout is what keeps the agent's prev_boards)
+        raise ValueError("a transitions=True agent evaluates with the fused rollout alone: leave fused_rollout on")
     for _ in range(max(int(eval_timesteps) - 1, 0)):
         env.step(agent.act(), auto_reset=False, write_boards=boards)
         env.reset_done()
@@ -206,15 +213,20 @@ def batched_default_eval(agent, env, eval_timesteps):
 
 
 BatchedRollout = collections.namedtuple("BatchedRollout", ["states", "actions", "rewards", "returns", "lengths"])
+# a transition body's rollout (BatchedPPOAgent(transitions=True)): prev_states is channel 0 of every observation, `states` channel 1
+TransitionRollout = collections.namedtuple("TransitionRollout", BatchedRollout._fields + ("prev_states",))
 
 
-def rollout_buffers(env, horizon=None):
-    """Device tensors one batched rollout needs (reusable across rollouts: a captured learner reads fixed addresses)."""
+def rollout_buffers(env, horizon=None, transitions=False):
+    """Device tensors one batched rollout needs (reusable across rollouts: a captured learner reads fixed addresses). transitions:
+    also "prev_states", the previous board of every step's observation."""
     import torch
 
     T = int(horizon or env.info.max_iterations)
     n, dev = env.n_envs, "cuda:%d" % env.device
-    return {"states": torch.empty((T, n, env.n_cells), dtype=torch.int8, device=dev),
+    extra = {"prev_states": torch.empty((T, n, env.n_cells), dtype=torch.int8, device=dev)} if transitions else {}
+    return {**extra,
+            "states": torch.empty((T, n, env.n_cells), dtype=torch.int8, device=dev),
             "actions": torch.empty((T, n), dtype=torch.uint8, device=dev),
             "recs": torch.empty((T, n, 4), dtype=torch.int8, device=dev),  # reward, hidden reward, done, actual action
             "rewards": torch.empty((n, T), dtype=torch.float32, device=dev),
@@ -246,8 +258,10 @@ def batched_gather_rollout(policy, env, discount, cheat=False, horizon=None, buf
     if fused is not None:
         weights, draw0 = fused()
         if "wh" in weights:  # a conv body (PPOCNNAgent): sgk_convq_rollout
+            prev = getattr(policy, "prev_boards", None)  # a transition body: fresh behind the reset above (sgk_convq_rollout_trans)
+            kw = {} if prev is None else {"prev_boards": prev, "prev_states": buf["prev_states"], "fresh": True}
             env.convq_rollout(weights, T, int(weights["b1"].numel()), mode="sample", draw_index0=draw0, auto_reset=False, states=states,
-                              actions=actions, recs=recs, mask_finished=True)
+                              actions=actions, recs=recs, mask_finished=True, **kw)
         else:
             env.policy_rollout(weights, T, mode="sample", draw_index0=draw0, auto_reset=False, states=states, actions=actions,
                                recs=recs, mask_finished=True)  # entries past an episode's end are stored as zeros by the kernel
@@ -305,6 +319,8 @@ def rollout_from_records(env, buf, discount, cheat=False, masked=False, gamma_po
     else:
         env.discounted_returns_members(rewards, gamma_pow, lengths=lengths, out=returns)
     env.reset()
+    if "prev_states" in buf:
+        return TransitionRollout(states, actions, rewards, returns, lengths, buf["prev_states"])
     return BatchedRollout(states, actions, rewards, returns, lengths)
 
 

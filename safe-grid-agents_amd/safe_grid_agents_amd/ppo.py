@@ -245,13 +245,20 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
     (off by default) the ppo-cnn shapes with 2 <= batch_size <= 64 learn on the device as well (sgk_ppo_cnn_epochs: three launches
     per epoch); every other case runs torch autograd.
 
+    transitions=True (ppo-cnn on BoatRace's 5 x 5 board; the reference's `trans-boat` agents): the policy acts on the observation of
+    TransitionBoatRace, [previous board, board] -- [board, board] at a reset -- through the two-channel kernels (sgk_convq_sample_trans,
+    sgk_convq_act_trans, sgk_convq_rollout_trans). `net` is then a PPOCNNAgent with two input channels, the agent owns `prev_boards`
+    (int8 [N, cells]: what the last fused rollout left, the previous boards of the observation the next action is chosen on; a caller
+    that steps the env itself copies the boards there before each step), the rollout carries `prev_states` beside `states`, and
+    learn() is the torch path (the fused conv learner has one input channel). Without the fused conv kernel there is no such form.
+
     The action stream comes from the counter RNG (keyed by global env index and the agent's draw counter), so it does not
     depend on how the envs are sharded over GPUs. `net` is a PPOMLPAgent / PPOCNNAgent on the env's device: its
     surrogate_loss / sync / old_policy are used as they are."""
 
     reads_boards = True  # acts on the materialised cells (batched_default_eval must keep writing them)
 
-    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True, fused_conv_learn=False):
+    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True, fused_conv_learn=False, transitions=False):
         import types
 
         cfg = types.SimpleNamespace(**vars(args))
@@ -259,7 +266,17 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         self.env = env
         self.device = cfg.device
         self.body = body
-        self.net = (PPOMLPAgent if body == "mlp" else PPOCNNAgent)(env, cfg)
+        self.transitions = bool(transitions)
+        net_env = env
+        if self.transitions:
+            if body != "cnn":
+                raise ValueError("transitions=True is the two-channel conv body: body must be 'cnn'")
+            if fused_conv_learn:
+                raise ValueError("fused_conv_learn=True with transitions=True: sgk_ppo_cnn_epochs has one input channel; learn() is the torch path")
+            # the observation space of TransitionBoatRace, (2, H, W), for the network alone: env.observation_space stays (1, H, W)
+            hw = tuple(int(v) for v in env.observation_space.shape[-2:])
+            net_env = types.SimpleNamespace(action_space=env.action_space, observation_space=types.SimpleNamespace(shape=(2,) + hw))
+        self.net = (PPOMLPAgent if body == "mlp" else PPOCNNAgent)(net_env, cfg)
         self.discount = float(args.discount)
         self.epochs, self.batch_size = int(args.epochs), int(args.batch_size)
         self.action_n = env.action_space.n
@@ -297,6 +314,12 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         self.fused_conv = (bool(fused_conv) and body == "cnn" and int(args.n_layers) == 2 and int(args.n_channels) in (4, 5, 8)
                            and self.action_n == 4
                            and tuple(int(v) for v in env.observation_space.shape[-2:]) in ((5, 5), (6, 5), (6, 6), (6, 8), (7, 7), (7, 8), (7, 9)))
+        if self.transitions:
+            if not (self.fused_conv and tuple(int(v) for v in env.observation_space.shape[-2:]) == (5, 5)):
+                raise ValueError("transitions=True needs the fused two-channel conv kernel: a 5 x 5 board (BoatRace), n_layers == 2, "
+                                 "n_channels in (4, 5, 8) and fused_conv=True")
+            self.prev_boards = torch.zeros((env.n_envs, env.n_cells), dtype=torch.int8, device=self.device)
+            self.prev_boards.copy_(env.boards().reshape(env.n_envs, -1))  # nothing has stepped: previous = current
         if self.fused_conv:
             self.n_channels = int(args.n_channels)
             self._cw_old, self._cw = self._conv_weights(self.net.old_policy), self._conv_weights(self.net)
@@ -319,7 +342,10 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
 
     def _observe(self):
         shape = (self.env.n_envs,) + tuple(self.env.observation_space.shape)
-        return self.env.obs_f32(out=self._obs).reshape(shape)
+        cur = self.env.obs_f32(out=self._obs).reshape(shape)
+        if self.transitions:  # [N, 2, H, W], previous first
+            return torch.cat((self.prev_boards.to(torch.float32).reshape(shape), cur), dim=1)
+        return cur
 
     def logits(self, old=False):
         """Actor logits [N, 4] of the current (or the old) policy for the env's current boards, by the torch forward."""
@@ -342,8 +368,12 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
     def act(self, boards=None):
         """PPOBaseAgent.act for every env: argmax of the current policy's logits (reference policy_base.py:47-52)."""
         if self.fused_conv and boards is None:
-            return self.env.convq_act(self._cw, 0.0, 0, self.n_channels, out=self._actions)  # epsilon 0: the argmax, first maximum
+            return self.env.convq_act(self._cw, 0.0, 0, self.n_channels, out=self._actions, **self._prev())  # epsilon 0: the argmax, first maximum
         return self.logits().argmax(-1).to(torch.uint8)
+
+    def _prev(self):
+        """The keyword the two-channel kernels need (nothing without transitions)."""
+        return {"prev_boards": self.prev_boards} if self.transitions else {}
 
     def act_explore(self, boards=None, out=None):
         """PPOBaseAgent.act_explore under the OLD policy, as gather_rollout uses it (reference policy_base.py:145)."""
@@ -351,7 +381,7 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         if self.fused_policy:
             self.env.policy_sample(self._fw, self.draws, out=out)
         elif self.fused_conv:
-            self.env.convq_sample(self._cw_old, self.draws, self.n_channels, out=out)
+            self.env.convq_sample(self._cw_old, self.draws, self.n_channels, out=out, **self._prev())
         else:
             self.env.categorical_sample(self.logits(old=True), self.draws, out=out)
         self.draws += 1
@@ -364,21 +394,28 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             return self.act_explore(out=out)
 
         policy.writes_out = True  # the draw kernel stores straight into the rollout's action row
+        if self.transitions and not self.fused_rollout:
+            raise ValueError("transitions=True gathers with the fused rollout alone (it is what keeps prev_boards): leave fused_rollout on")
         if self._buffers is None or (horizon is not None and int(horizon) != self._buffers["actions"].shape[0]):
-            self._buffers, self._graph = rollout_buffers(self.env, horizon), None
+            self._buffers, self._graph = rollout_buffers(self.env, horizon, transitions=self.transitions), None
             self._gather_graph, self._gathers = None, 0
         steps = self._buffers["actions"].shape[0]
         if (self.fused_policy or self.fused_conv) and self.fused_rollout:  # forward + draw + env.step of all steps in ONE launch
             first_draw = self.draws
             weights = self._fw if self.fused_policy else self._cw_old
             policy.fused_rollout = lambda: (weights, first_draw)
+            if self.transitions:
+                policy.prev_boards = self.prev_boards  # the gather's reset makes them fresh; the closing reset does so again
             self.draws += steps
         elif not self.fused_policy and self.graph_gather and self._gathers >= 1 and getattr(self.env, "_bound", False):
             # the first rollout ran eagerly (lazy initialisation done); from the second on the whole step loop is one graph
             policy.run_steps = self._replay_gather
         self._gathers += 1
-        return batched_gather_rollout(policy, self.env, self.discount, cheat=cheat, horizon=horizon, buffers=self._buffers,
-                                      filter_rewards=getattr(self, "_filter_rewards", None))  # (a subclass's hook: crmdp.py)
+        rollout = batched_gather_rollout(policy, self.env, self.discount, cheat=cheat, horizon=horizon, buffers=self._buffers,
+                                         filter_rewards=getattr(self, "_filter_rewards", None))  # (a subclass's hook: crmdp.py)
+        if self.transitions:  # behind the gather's closing reset: previous = current
+            self.prev_boards.copy_(self.env.boards().reshape(self.env.n_envs, -1))
+        return rollout
 
     def _gather_steps(self):
         """The lockstep steps of one rollout for a body without a fused kernel, five launches + the torch forward per step:
@@ -434,6 +471,8 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             t_sel, n_sel = t_ix[pick], n_ix[pick]
         shape = tuple(self.env.observation_space.shape)
         s = rollout.states[t_sel, n_sel].to(torch.float32).reshape((-1,) + shape)
+        if self.transitions:  # [B, 2, H, W], previous first
+            s = torch.cat((rollout.prev_states[t_sel, n_sel].to(torch.float32).reshape((-1,) + shape), s), dim=1)
         return s, rollout.actions[t_sel, n_sel].to(torch.long), rollout.returns[n_sel, t_sel]
 
     def _epochs_on_device(self, rollout):

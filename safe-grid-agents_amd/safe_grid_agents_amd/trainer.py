@@ -99,6 +99,10 @@ _HASH_CONSENSUS = ("hash-consensus-eval", "HCE", dict(action="store_true", defau
 # equals the reference's unbounded dictionary whatever capacity it started with. Absent unless given; another level stops the run with a
 # message (check_hash_grow)
 _HASH_GROW = ("hash-grow", "HG", dict(action="store_true", default=argparse.SUPPRESS))
+# extension, batched trainer (-N) on trans-boat only: `--transition-policy` gives ppo-cnn / ppo-crmdp the reference's two-channel body,
+# acting on [previous board, board] as TransitionBoatRace shows it (BatchedPPOAgent(transitions=True): the parity form). Absent unless
+# given; another level stops the run with a message (check_transition_policy)
+_TRANSITION_POLICY = ("transition-policy", "TP", dict(action="store_true", default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -118,9 +122,10 @@ _AGENT_FLAGS = {
                ("n-channels", "ch", dict(type=int, default=5)),
                _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
     "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
-    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
+    "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE,
+                                                                         _TRANSITION_POLICY] + _PBT,
     # the reference's flags (agent_parser_configs.yaml:124-135) and no more: one agent, no population of it
-    "ppo-crmdp": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG],
+    "ppo-crmdp": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _TRANSITION_POLICY],
 }
 
 
@@ -240,6 +245,7 @@ def train_batched(args, writer_factory=None, reporter=_noop):
     if check_hash_consensus_eval(args):  # --hash-consensus-eval: the same scalars and closing line, voted by board key (tomato)
         consensus = {"hashed": True}
     hash_grow = check_hash_grow(args)  # --hash-grow: True / False; SystemExit on a level whose tables are not hashed
+    transitions = check_transition_policy(args)  # --transition-policy: True / False; SystemExit off trans-boat or with --members
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if consensus is not None and world > 1:
@@ -283,14 +289,14 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         import torch
 
         torch.manual_seed(args.seed or 0)
-        agent = BatchedPPOAgent(env, args, body=args.agent_alias[4:])
+        agent = BatchedPPOAgent(env, args, body=args.agent_alias[4:], **({"transitions": True} if transitions else {}))
     elif args.agent_alias == "ppo-crmdp":  # ppo-cnn with the corrupt-reward filter between the gather and the returns (crmdp.py)
         import torch
 
         from .crmdp import BatchedPPOCRMDPAgent
 
         torch.manual_seed(args.seed or 0)
-        agent = BatchedPPOCRMDPAgent(env, args)
+        agent = BatchedPPOCRMDPAgent(env, args, **({"transitions": True} if transitions else {}))
     elif args.agent_alias == "deep-q":
         import torch
 
@@ -409,6 +415,20 @@ def check_hash_grow(args):
     if args.env_alias != "tomato":
         raise SystemExit("--hash-grow runs on tomato only: %s has a perfect hash of its boards, its tables have no capacity to grow"
                          % (args.env_alias,))
+    return True
+
+
+def check_transition_policy(args):
+    """--transition-policy of `args` -> True / False. SystemExit with a plain message for an agent without the conv body, for a level
+    other than trans-boat (no other level observes transitions) and together with --members (the populations have no such form)."""
+    if not getattr(args, "transition_policy", False):
+        return False
+    if args.agent_alias not in ("ppo-cnn", "ppo-crmdp"):
+        raise SystemExit("--transition-policy is the two-channel conv body of ppo-cnn and ppo-crmdp, not %r" % (args.agent_alias,))
+    if args.env_alias != "trans-boat":
+        raise SystemExit("--transition-policy runs on trans-boat only: %s observes one board, not a transition" % (args.env_alias,))
+    if int(getattr(args, "members", 0) or 0):
+        raise SystemExit("--transition-policy has no population form: drop --members")
     return True
 
 
