@@ -847,6 +847,24 @@ SGK_API int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *learner);
 /* The workspace sgk_ppo_cnn_epochs needs on this handle's level, in bytes; -1 (sgk_last_error says why) for an unsupported n_channels,
  * board shape or batch. */
 SGK_API int64_t sgk_ppo_cnn_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch);
+/* sgk_ppo_cnn_epochs for the two-board body (the reference's `trans-boat` agents; the learner of what sgk_convq_act_trans /
+ * sgk_convq_sample_trans / sgk_convq_rollout_trans act with): the network reads [previous board, board], so
+ *     trunk  = relu(conv3x3(relu(conv3x3(x, 2 -> C)), C -> C)) + conv1x1(x, 2 -> C)
+ * with plane 0 of a row the previous board from `prev_states` -- int8 [horizon][n_trajectories][n_cells], the prev_states_out_dev of
+ * sgk_convq_rollout_trans -- and plane 1 the board from learner->states, both at the same flat row step * n_trajectories + trajectory.
+ * `learner` keeps its layout; as with sgk_convq_weights in the _trans acting calls the caller vouches for the two larger tensors:
+ * params[0], m[0], v[0] and old_params[0] (network.0.0.weight [C][2][3][3]) are 18 C floats, index 4 of each (bottleneck.weight
+ * [C][2][1][1]) 2 C floats. Everything else is sgk_ppo_cnn_epochs': the same three launches per epoch, the same row draw (the rows do
+ * not depend on the channel count), loss, Adam and step counter; deterministic, no float atomics, no allocation, no host
+ * synchronisation, can be recorded in a graph. The single learner only (no member form), 5x5 boards, n_channels 4, 5 or 8,
+ * 2 <= batch <= 64. workspace: sgk_ppo_cnn_trans_workspace_bytes(h, n_channels, batch) bytes, 8-byte aligned, owned by the caller.
+ * SGK_ERR_INVALID, with a message and nothing launched, for prev_states == NULL, a board other than 5x5 and whatever
+ * sgk_ppo_cnn_epochs refuses. */
+SGK_API int sgk_ppo_cnn_epochs_trans(sgk_env *h, const sgk_ppo_cnn_learner *learner, const int8_t *prev_states);
+/* The workspace sgk_ppo_cnn_epochs_trans needs, in bytes: 4 * (1088 + batch * (5 * C * 25 + P2)) with P2 = P + 10 * C and
+ * P = 27 * C * C + 140 * C + 5 the one-board parameter count on 25 cells (530 432 bytes at C = 5, batch 64); -1 (sgk_last_error says
+ * why) for the shapes sgk_ppo_cnn_epochs_trans refuses. */
+SGK_API int64_t sgk_ppo_cnn_trans_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch);
 /* sgk_ppo_cnn_epochs for n_members INDEPENDENT PPOCNNAgents: the same three launches per epoch with a member axis on the grid (forward
  * and backward batch x n_members workgroups, Adam ceil(P / 256) x n_members); member m is the reference's run on the trajectories m * E
  * .. (m + 1) * E - 1, E = n_trajectories / n_members. Every tensor of `learner` but the rollout exists once per member, stacked on a

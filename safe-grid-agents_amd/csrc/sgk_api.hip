@@ -1303,11 +1303,26 @@ int64_t sgk_ppo_cnn_members_workspace_bytes(sgk_env *h, int32_t n_channels, int3
   return (int64_t)n_members * (int64_t)sgk::ppo_cnn_members_stride_bytes(H, W, n_channels, batch);
 } SGK_CATCH_VALUE(-1)
 
-// sgk_ppo_cnn_epochs (n_members 0: its own kernels, the handle's seed) and sgk_ppo_cnn_epochs_members: the same checks
+int64_t sgk_ppo_cnn_trans_workspace_bytes(sgk_env *h, int32_t n_channels, int32_t batch) try {
+  if (!h) return (int64_t)fail(SGK_ERR_INVALID, "handle is NULL");
+  const int H = h->sh.rules_host.height, W = h->sh.rules_host.width;
+  if (!sgk::ppo_cnn_trans_shape_supported(H, W, n_channels) || batch < 2 || batch > 64) {
+    fail(SGK_ERR_INVALID, "sgk_ppo_cnn_trans_workspace_bytes needs n_channels 4, 5 or 8, 2 <= batch <= 64 and a 5x5 board (this level: "
+                          "%dx%d, n_channels %d, batch %d)", H, W, (int)n_channels, (int)batch);
+    return -1;
+  }
+  return (int64_t)sgk::ppo_cnn_workspace_bytes(H, W, n_channels, batch, 2);
+} SGK_CATCH_VALUE(-1)
+
+// sgk_ppo_cnn_epochs (n_members 0: its own kernels, the handle's seed), sgk_ppo_cnn_epochs_members and sgk_ppo_cnn_epochs_trans
+// (trans: the two-board kernels on prev_states; n_members 0): the same checks
 static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,
-                               const sgk_ppo_member_hyper *hyper_dev = nullptr) {
+                               const sgk_ppo_member_hyper *hyper_dev = nullptr, bool trans = false, const int8_t *prev_states = nullptr) {
   SGK_CHECK_HANDLE(h);
   if (!L) return fail(SGK_ERR_INVALID, "learner is NULL");
+  if (trans && !prev_states)
+    return fail(SGK_ERR_INVALID, "prev_states is NULL: sgk_ppo_cnn_epochs_trans reads the previous board of every row (sgk_convq_rollout_trans' "
+                                 "prev_states_out_dev)");
   if (!L->workspace && n_members > 0)
     return fail(SGK_ERR_INVALID, "workspace is NULL: sgk_ppo_cnn_epochs_members works in the caller's sgk_ppo_cnn_members_workspace_bytes()");
   const void *need[] = {L->states, L->actions, L->returns, L->lengths, L->step, L->workspace};
@@ -1321,6 +1336,8 @@ static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t
   if (!sgk::ppo_cnn_shape_supported(H, W, L->n_channels))
     return fail(SGK_ERR_INVALID, "sgk_ppo_cnn_epochs needs n_channels 4, 5 (the reference default) or 8 and a board of 5x5, 6x5, 6x6, 6x8, "
                                  "7x7, 7x8 or 7x9 (this level: %dx%d, n_channels %d)", H, W, L->n_channels);
+  if (trans && !sgk::ppo_cnn_trans_shape_supported(H, W, L->n_channels))
+    return fail(SGK_ERR_INVALID, "sgk_ppo_cnn_epochs_trans needs a 5x5 board, the boards sgk_convq_rollout_trans acts on (this level: %dx%d)", H, W);
   if (L->batch < 2 || L->batch > 64 || L->n_epochs < 1 || L->horizon < 1 || L->n_trajectories < 1 || L->n_trajectories >= (1ll << 31))
     return fail(SGK_ERR_INVALID, "sgk_ppo_cnn_epochs needs 2 <= batch <= 64, n_epochs >= 1, horizon >= 1, 1 <= n_trajectories < 2^31");
   sgk::PpoCnnLearner d;
@@ -1336,12 +1353,20 @@ static int ppo_cnn_epochs_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t
   d.workspace = L->workspace;
   d.lr = L->lr; d.beta1 = L->beta1; d.beta2 = L->beta2; d.eps = L->eps;
   d.clipping = L->clipping; d.critic_coeff = L->critic_coeff; d.entropy_bonus = L->entropy_bonus;
+  if (trans) {
+    SGK_HIP(sgk::launch_ppo_cnn_epochs_trans(h->sh, d, prev_states, h->stream));
+    return SGK_OK;
+  }
   SGK_HIP(sgk::launch_ppo_cnn_epochs(h->sh, d, h->stream, n_members, member_keys_dev,
                                      reinterpret_cast<const sgk::PpoMemberHyper *>(hyper_dev)));
   return SGK_OK;
 }
 
 int sgk_ppo_cnn_epochs(sgk_env *h, const sgk_ppo_cnn_learner *L) try { return ppo_cnn_epochs_impl(h, L, 0, nullptr); } SGK_CATCH_STATUS
+
+int sgk_ppo_cnn_epochs_trans(sgk_env *h, const sgk_ppo_cnn_learner *L, const int8_t *prev_states) try {
+  return ppo_cnn_epochs_impl(h, L, 0, nullptr, nullptr, true, prev_states);
+} SGK_CATCH_STATUS
 
 // sgk_ppo_cnn_epochs_members' own checks, then the shared ones (hyper_dev: sgk_ppo_cnn_epochs_members_hyper's)
 static int ppo_cnn_epochs_members_impl(sgk_env *h, const sgk_ppo_cnn_learner *L, int32_t n_members, const uint64_t *member_keys_dev,

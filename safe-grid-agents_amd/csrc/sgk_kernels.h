@@ -226,7 +226,8 @@ struct PpoCnnLearner {
   double lr, beta1, beta2, eps, clipping, critic_coeff, entropy_bonus;
 };
 bool ppo_cnn_shape_supported(int height, int width, int n_channels);
-size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch);
+// in_channels 2: the two-board form's (sgk_ppo_cnn_epochs_trans): 10 * n_channels more gradient floats per sample
+size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch, int in_channels = 1);
 size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int batch);  // one member's slice: the above, 8-byte padded
 // n_members >= 1 (sgk_ppo_cnn_epochs_members; 0: sgk_ppo_cnn_epochs' own kernels): the member instantiation of the three kernels, a
 // member axis on the grid. Every tensor of P but the rollout is stacked [n_members][...] and P addresses member 0, the workspace is
@@ -235,6 +236,10 @@ size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int b
 // member_hyper (with n_members >= 1): as for launch_ppo_epochs, read by the backward and Adam launches
 hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members = 0,
                                  const uint64_t *member_keys = nullptr, const PpoMemberHyper *member_hyper = nullptr);
+// sgk_ppo_cnn_epochs_trans: the single learner on [previous board, board]; P.p[0] / m / v / o[0] are 18 C floats, index 4 of each 2 C;
+// prev_states int8 [horizon][n_trajectories][cells] beside P.states. 5 x 5 boards only (ppo_cnn_trans_shape_supported)
+bool ppo_cnn_trans_shape_supported(int height, int width, int n_channels);
+hipError_t launch_ppo_cnn_epochs_trans(const Shard &sh, const PpoCnnLearner &P, const int8_t *prev_states, hipStream_t st);
 // member_envs > 0: gamma_pow is a table [n / member_envs][t_max] and trajectory i reads row i / member_envs; 0: one row for all
 hipError_t launch_discounted_returns(const Shard &sh, const float *rewards, const int32_t *lengths, const float *gamma_pow,
                                      float *returns, int64_t n, int t_max, hipStream_t st, int64_t member_envs = 0);

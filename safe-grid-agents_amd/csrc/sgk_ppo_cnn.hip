@@ -23,6 +23,11 @@
 // runs in a fixed order: a call is deterministic and a captured replay equals the eager call bit for bit.
 // sgk_ppo_cnn_epochs_members: the same three launches for n_members independent learners, the member on blockIdx.y (the MEMBERS
 // instantiations below); every member works in its own slice of the workspace and reads only its own samples.
+// sgk_ppo_cnn_epochs_trans: the same three launches for the two-board body (the CIN = 2 instantiations; 5 x 5 boards, the single
+// learner): x is [previous board, board] -- two adjacent padded planes, the previous board from `prev_states` at the same flat row --
+// conv1 is 2 -> C, the trunk's residual wb[co][0] x0 + wb[co][1] x1 + bb[co], the bottleneck's weight gradient 2 C entries. The row
+// draw, the loss arithmetic, pc_adam and the step counter are the one-plane form's code. LDS at C = 8: forward 28.7 KB ((2 + 5 C)
+// planes of 49 floats, 2 933 + 2 148 parameters), backward 27.9 KB ((2 + 10 C) planes, 2 933 parameters).
 #include <algorithm>
 
 #include "sgk_device.h"
@@ -35,30 +40,34 @@ constexpr int PC_WG = 256;
 constexpr int PC_SC = 16;  // floats of per-sample scalars in the workspace: logits [0..3], value [4], old logits [5..8], return [9],
                            // action [10] (int), row [12..13] (int64)
 
-template <int HH, int WW, int C>
+// CIN: the board planes the network reads. 1: the board; 2 (sgk_ppo_cnn_epochs_trans): [previous board, board], network.0.0.weight
+// [C][2][3][3] and bottleneck.weight [C][2][1][1] -- every later offset, P and PO move by 10 C, nothing else changes shape.
+template <int HH, int WW, int C, int CIN = 1>
 struct PcGeom {
-  static constexpr int NC = HH * WW, NF = C * NC;
+  static constexpr int NC = HH * WW, NF = C * NC, CI = CIN;
   static constexpr int PW = WW + 2, PL = (HH + 2) * PW;  // a plane with a zero border
   static constexpr int K2 = 9 * C * C;
   // the 14 parameter tensors in registration order, flattened back to back: network.0.0, network.1.0.0, bottleneck, actor_cnn.0,
   // actor_linear, critic_cnn.0, critic_linear (weight, bias each). The old policy's 10 actor-path tensors are the first 10.
-  static constexpr int o_w1 = 0, o_b1 = o_w1 + 9 * C, o_w2 = o_b1 + C, o_b2 = o_w2 + K2, o_wb = o_b2 + C, o_bb = o_wb + C,
+  static constexpr int o_w1 = 0, o_b1 = o_w1 + 9 * C * CIN, o_w2 = o_b1 + C, o_b2 = o_w2 + K2, o_wb = o_b2 + C, o_bb = o_wb + C * CIN,
                        o_wa = o_bb + C, o_ba = o_wa + K2, o_la = o_ba + C, o_lab = o_la + 4 * NF, o_wv = o_lab + 4, o_bv = o_wv + K2,
                        o_lv = o_bv + C, o_lvb = o_lv + NF, P = o_lvb + 1, PO = o_wv;
-  // LDS planes
-  static constexpr int X = 0, H1 = 1, H2 = 1 + C, TR = 1 + 2 * C, AH = 1 + 3 * C, CH = 1 + 4 * C, ACT_PLANES = 1 + 5 * C;
+  // LDS planes (X: CIN adjacent board planes, the current board last)
+  static constexpr int X = 0, H1 = CIN, H2 = CIN + C, TR = CIN + 2 * C, AH = CIN + 3 * C, CH = CIN + 4 * C, ACT_PLANES = CIN + 5 * C;
   static constexpr int GA = ACT_PLANES, GC = GA + C, DT = GC + C, G2 = DT + C, G1 = G2 + C, BWD_PLANES = G1 + C;
   static constexpr int SAVE = 5 * C * NC;  // activations saved per sample: h1, relu(conv2), trunk, actor head, critic head
 };
 
-__host__ __device__ constexpr int pc_params(int H, int W, int C) { return 9 * C + C + 3 * (9 * C * C + C) + C + C + 5 * C * H * W + 5; }
+__host__ __device__ constexpr int pc_params(int H, int W, int C, int cin = 1) {
+  return 9 * C * cin + C + 3 * (9 * C * C + C) + C * cin + C + 5 * C * H * W + 5;
+}
 
 // workspace: [0..63] header (the step counter at the epoch's start, int64) | per-sample scalars [64][PC_SC] | activations [batch][SAVE]
 // | per-sample gradients [batch][P]
 constexpr size_t PC_HDR = 64, PC_SCAL = 64 * PC_SC;
 
-size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch) {
-  const size_t save = (size_t)5 * n_channels * height * width, p = (size_t)pc_params(height, width, n_channels);
+size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch, int in_channels) {
+  const size_t save = (size_t)5 * n_channels * height * width, p = (size_t)pc_params(height, width, n_channels, in_channels);
   return sizeof(float) * (PC_HDR + PC_SCAL + (size_t)batch * (save + p));
 }
 
@@ -66,6 +75,12 @@ size_t ppo_cnn_workspace_bytes(int height, int width, int n_channels, int batch)
 // and rows stay 8-byte aligned
 size_t ppo_cnn_members_stride_bytes(int height, int width, int n_channels, int batch) {
   return (ppo_cnn_workspace_bytes(height, width, n_channels, batch) + 7) & ~(size_t)7;
+}
+
+template <class G>
+__device__ __forceinline__ int pc_cell(int cell) {  // interior cell -> its offset inside a padded plane
+  const int y = cell / (G::PW - 2), x = cell - y * (G::PW - 2);
+  return (y + 1) * G::PW + x + 1;
 }
 
 struct PpoCnnArgs {
@@ -96,6 +111,16 @@ struct PpoCnnArgs {
   // entropy_bonus instead of the four above
   const PpoMemberHyper *member_hyper;
 };
+// the two-plane kernels' argument (sgk_ppo_cnn_epochs_trans): the new pointer behind everything above. A type of its own, because
+// `epoch` follows the struct in the forward and backward kernels' argument lists: a member appended to PpoCnnArgs itself would move
+// that offset in every one-plane kernel.
+struct PpoCnnTransArgs : PpoCnnArgs {
+  const int8_t *prev_states;  // int8 [T][N][cells]: plane 0 of row t * N + n (plane 1 is `states`)
+};
+template <int CIN>
+struct PcArgs { typedef PpoCnnArgs type; };
+template <>
+struct PcArgs<2> { typedef PpoCnnTransArgs type; };
 
 // this workgroup's member (0 without the member axis) and what it owns
 template <bool MEMBERS>
@@ -122,14 +147,9 @@ __device__ __forceinline__ void pc_stage(float *dst, const float *const *src, in
   }
 }
 
-template <class G>
-__device__ __forceinline__ int pc_cell(int cell) {  // interior cell -> its offset inside a padded plane
-  const int y = cell / (G::PW - 2), x = cell - y * (G::PW - 2);
-  return (y + 1) * G::PW + x + 1;
-}
-
 // out[co] = act(b[co] + sum_{ci, ky, kx} w[co][ci][ky][kx] in[ci](y + ky - 1, x + kx - 1)), one lane per (co, cell).
-// MODE 0: ReLU; MODE 1: ReLU, and the trunk plane trunk_out[co] = that + wb[co] * x + bb[co] as well (out = relu(conv2) is kept)
+// MODE 0: ReLU; MODE 1: ReLU, and the trunk plane trunk_out[co] = that + sum_k wb[co][k] * x_k + bb[co] over the G::CI board planes
+// (summed from the last plane to the first) as well (out = relu(conv2) is kept)
 template <class G, int CIN, int C, int MODE>
 __device__ __forceinline__ void pc_conv(float *act, int in_plane, int out_plane, const float *w, const float *b, const float *wb = nullptr,
                                         const float *bb = nullptr, int trunk_plane = 0) {
@@ -147,7 +167,12 @@ __device__ __forceinline__ void pc_conv(float *act, int in_plane, int out_plane,
     }
     const float r = fmaxf(acc, 0.0f);
     act[(out_plane + co) * G::PL + c0 + G::PW + 1] = r;
-    if (MODE == 1) act[(trunk_plane + co) * G::PL + c0 + G::PW + 1] = r + fmaf(wb[co], act[G::X * G::PL + c0 + G::PW + 1], bb[co]);
+    if constexpr (MODE == 1 && G::CI == 2) {
+      const float x0 = act[G::X * G::PL + c0 + G::PW + 1], x1 = act[(G::X + 1) * G::PL + c0 + G::PW + 1];
+      act[(trunk_plane + co) * G::PL + c0 + G::PW + 1] = r + fmaf(wb[2 * co], x0, fmaf(wb[2 * co + 1], x1, bb[co]));
+    } else if (MODE == 1) {
+      act[(trunk_plane + co) * G::PL + c0 + G::PW + 1] = r + fmaf(wb[co], act[G::X * G::PL + c0 + G::PW + 1], bb[co]);
+    }
   }
 }
 
@@ -179,10 +204,10 @@ __device__ __forceinline__ void pc_linear(const float *act, int plane, const flo
   __syncthreads();
 }
 
-// the trunk of the network whose flat parameters are at `w`, on the board in plane X: h1, relu(conv2) and the trunk planes
+// the trunk of the network whose flat parameters are at `w`, on the board planes at X: h1, relu(conv2) and the trunk planes
 template <class G, int C>
 __device__ __forceinline__ void pc_trunk(float *act, const float *w) {
-  pc_conv<G, 1, C, 0>(act, G::X, G::H1, w + G::o_w1, w + G::o_b1);
+  pc_conv<G, G::CI, C, 0>(act, G::X, G::H1, w + G::o_w1, w + G::o_b1);
   __syncthreads();
   pc_conv<G, C, C, 1>(act, G::H1, G::H2, w + G::o_w2, w + G::o_b2, w + G::o_wb, w + G::o_bb, G::TR);
   __syncthreads();
@@ -190,9 +215,11 @@ __device__ __forceinline__ void pc_trunk(float *act, const float *w) {
 
 // MEMBERS = false: sgk_ppo_cnn_epochs' kernels, grid (batch) resp. (ceil(P / 256)); MEMBERS = true: sgk_ppo_cnn_epochs_members', a
 // member axis blockIdx.y on the same grids (with one member too). The arithmetic of a sample does not depend on the flag.
-template <int HH, int WW, int C, bool MEMBERS>
-__global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, int epoch) {
-  typedef PcGeom<HH, WW, C> G;
+// CIN = 2 (sgk_ppo_cnn_epochs_trans; the single learner only): two board planes, the previous board from a.prev_states.
+template <int HH, int WW, int C, bool MEMBERS, int CIN = 1>
+__global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(typename PcArgs<CIN>::type a, int epoch) {
+  static_assert(CIN == 1 || !MEMBERS, "the two-plane form has no member axis");
+  typedef PcGeom<HH, WW, C, CIN> G;
   __shared__ __attribute__((aligned(16))) float act[G::ACT_PLANES * G::PL];
   __shared__ __attribute__((aligned(16))) float wcur[G::P];
   __shared__ __attribute__((aligned(16))) float wold[G::PO];
@@ -256,9 +283,13 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_forward_kernel(PpoCnnArgs a, in
   pc_stage<G>(wcur, a.p, 14, mem);
   pc_stage<G>(wold, a.o, 10, mem);
   __syncthreads();
-  {
+  {  // the board: the last of the CIN planes at X; the previous board in front of it
     const int8_t *board = a.states + row_s * G::NC;
-    for (int i = t; i < G::NC; i += PC_WG) act[G::X * G::PL + pc_cell<G>(i)] = (float)board[i];
+    for (int i = t; i < G::NC; i += PC_WG) act[(G::X + CIN - 1) * G::PL + pc_cell<G>(i)] = (float)board[i];
+    if constexpr (CIN == 2) {
+      const int8_t *prev = a.prev_states + row_s * G::NC;
+      for (int i = t; i < G::NC; i += PC_WG) act[G::X * G::PL + pc_cell<G>(i)] = (float)prev[i];
+    }
   }
   __syncthreads();
   // ---- the old policy: trunk + actor (no gradient) ----
@@ -329,10 +360,11 @@ __device__ __forceinline__ void pc_input_grad(const float *act, int g_plane, con
 
 // HYPER = true (with MEMBERS; sgk_ppo_cnn_epochs_members_hyper): the member coordinate loads its element of a.member_hyper once at
 // entry -- a wave-uniform load -- and converts each field with the host's (float) cast. The forward kernel reads none of the four.
-template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
-__global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, int epoch) {
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false, int CIN = 1>
+__global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(typename PcArgs<CIN>::type a, int epoch) {
   static_assert(MEMBERS || !HYPER, "per-member hyper-parameters come with the member axis");
-  typedef PcGeom<HH, WW, C> G;
+  static_assert(CIN == 1 || !MEMBERS, "the two-plane form has no member axis");
+  typedef PcGeom<HH, WW, C, CIN> G;
   __shared__ __attribute__((aligned(16))) float act[G::BWD_PLANES * G::PL];
   __shared__ __attribute__((aligned(16))) float w[G::P];
   __shared__ float dout[8];
@@ -350,7 +382,11 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, i
   {
     const long long row = *reinterpret_cast<const long long *>(scal + b * PC_SC + 12);
     const int8_t *board = a.states + row * G::NC;
-    for (int i = t; i < G::NC; i += PC_WG) act[G::X * G::PL + pc_cell<G>(i)] = (float)board[i];
+    for (int i = t; i < G::NC; i += PC_WG) act[(G::X + CIN - 1) * G::PL + pc_cell<G>(i)] = (float)board[i];
+    if constexpr (CIN == 2) {
+      const int8_t *prev = a.prev_states + row * G::NC;
+      for (int i = t; i < G::NC; i += PC_WG) act[G::X * G::PL + pc_cell<G>(i)] = (float)prev[i];
+    }
     const float *save = ws + PC_HDR + PC_SCAL + (size_t)b * G::SAVE;
     for (int i = t; i < G::SAVE; i += PC_WG) {
       const int pl = i / G::NC, cell = i - pl * G::NC;
@@ -442,8 +478,19 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, i
     act[(G::G2 + ci) * G::PL + o] = act[(G::H2 + ci) * G::PL + o] > 0.0f ? d : 0.0f;  // the residual split: relu(conv2)'s share
   });
   __syncthreads();
-  // ---- the bottleneck (1 x 1 on the board) and conv2 ----
-  if (t < 2 * C) {
+  // ---- the bottleneck (1 x 1 on the board planes: entry [c][k] = d_trunk[c] . x_k, cells in order) and conv2 ----
+  if constexpr (CIN == 2) {
+    if (t < 3 * C) {
+      const int c = t < 2 * C ? t >> 1 : t - 2 * C;
+      const float *dp = act + (G::DT + c) * G::PL, *xp = act + (G::X + (t & 1)) * G::PL;
+      float acc = 0.0f;
+      for (int cell = 0; cell < G::NC; ++cell) {
+        const int o = pc_cell<G>(cell);
+        acc = t < 2 * C ? fmaf(dp[o], xp[o], acc) : acc + dp[o];
+      }
+      g[t < 2 * C ? G::o_wb + t : G::o_bb + c] = acc;
+    }
+  } else if (t < 2 * C) {
     const int c = t % C;
     const float *dp = act + (G::DT + c) * G::PL;
     float acc = 0.0f;
@@ -459,7 +506,7 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_backward_kernel(PpoCnnArgs a, i
   });
   __syncthreads();
   // ---- conv1 (no input gradient) ----
-  pc_wgrad<G, 1, C>(act, G::G1, G::X, g + G::o_w1, g + G::o_b1);
+  pc_wgrad<G, G::CI, C>(act, G::G1, G::X, g + G::o_w1, g + G::o_b1);
 }
 
 __device__ __forceinline__ float pc_adam(float p, float &m, float &v, float g, float lr_bc1, float inv_bc2_sqrt, float beta1, float beta2,
@@ -469,10 +516,10 @@ __device__ __forceinline__ float pc_adam(float p, float &m, float &v, float g, f
   return p - lr_bc1 * (m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * inv_bc2_sqrt + eps));  // (sgk_ppo_epochs' adam_plain)
 }
 
-template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
-__global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(PpoCnnArgs a) {
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false, int CIN = 1>
+__global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(typename PcArgs<CIN>::type a) {
   static_assert(MEMBERS || !HYPER, "per-member hyper-parameters come with the member axis");
-  typedef PcGeom<HH, WW, C> G;
+  typedef PcGeom<HH, WW, C, CIN> G;
   const int e = blockIdx.x * PC_WG + threadIdx.x;
   const size_t mem = pc_member<MEMBERS>();
   if constexpr (HYPER) a.lr = (float)a.member_hyper[mem].lr;
@@ -506,31 +553,30 @@ bool ppo_cnn_shape_supported(int height, int width, int n_channels) {
   return shape && (n_channels == 4 || n_channels == 5 || n_channels == 8);
 }
 
-template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false>
-static hipError_t launch_ppo_cnn_shape(const PpoCnnArgs &a, int n_epochs, int n_members, hipStream_t st) {
-  typedef PcGeom<HH, WW, C> G;
-  static_assert(G::P == pc_params(HH, WW, C), "parameter map");
+template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false, int CIN = 1>
+static hipError_t launch_ppo_cnn_shape(const typename PcArgs<CIN>::type &a, int n_epochs, int n_members, hipStream_t st) {
+  typedef PcGeom<HH, WW, C, CIN> G;
+  static_assert(G::P == pc_params(HH, WW, C, CIN), "parameter map");
+  static_assert(G::P == PcGeom<HH, WW, C>::P + 10 * C * (CIN - 1) && G::PO == PcGeom<HH, WW, C>::PO + 10 * C * (CIN - 1), "the second plane's share");
   const unsigned ny = MEMBERS ? (unsigned)n_members : 1u;
   for (int epoch = 0; epoch < n_epochs; ++epoch) {
-    ppo_cnn_forward_kernel<HH, WW, C, MEMBERS><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_backward_kernel<HH, WW, C, MEMBERS, HYPER><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
-    ppo_cnn_adam_kernel<HH, WW, C, MEMBERS, HYPER><<<dim3((G::P + PC_WG - 1) / PC_WG, ny), dim3(PC_WG), 0, st>>>(a);
+    ppo_cnn_forward_kernel<HH, WW, C, MEMBERS, CIN><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
+    ppo_cnn_backward_kernel<HH, WW, C, MEMBERS, HYPER, CIN><<<dim3(a.batch, ny), dim3(PC_WG), 0, st>>>(a, epoch);
+    ppo_cnn_adam_kernel<HH, WW, C, MEMBERS, HYPER, CIN><<<dim3((G::P + PC_WG - 1) / PC_WG, ny), dim3(PC_WG), 0, st>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys,
-                                 const PpoMemberHyper *member_hyper) {
-  (void)hipGetLastError();
-  const int H = sh.rules_host.height, W = sh.rules_host.width, C = P.n_channels;
-  if (!ppo_cnn_shape_supported(H, W, C) || P.batch < 2 || P.batch > 64 || P.n_epochs < 1 || P.horizon < 1 || P.n_trajectories < 1 ||
-      P.n_trajectories >= (1ll << 31) || !P.workspace)
-    return hipErrorInvalidValue;
-  if (n_members < 0 || n_members > 65535 || (n_members > 0 && P.n_trajectories % n_members != 0)) return hipErrorInvalidValue;  // (gridDim.y)
-  if (member_hyper && n_members < 1) return hipErrorInvalidValue;
-  PpoCnnArgs a;
+// what both entry points refuse
+static bool pc_learner_ok(const PpoCnnLearner &P) {
+  return P.batch >= 2 && P.batch <= 64 && P.n_epochs >= 1 && P.horizon >= 1 && P.n_trajectories >= 1 && P.n_trajectories < (1ll << 31) &&
+         P.workspace;
+}
+
+// the kernels' argument from the learner (everything but what the member and two-plane forms add)
+static void pc_fill_args(PpoCnnArgs &a, const Shard &sh, const PpoCnnLearner &P) {
   a.states = P.states; a.actions = P.actions; a.returns = P.returns; a.lengths = P.lengths;
   a.T = P.horizon; a.N = P.n_trajectories;
   for (int i = 0; i < 14; ++i) { a.p[i] = P.p[i]; a.m[i] = P.m[i]; a.v[i] = P.v[i]; }
@@ -540,6 +586,22 @@ hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStr
   a.batch = P.batch; a.seed = sh.seed;
   a.lr = (float)P.lr; a.beta1 = (float)P.beta1; a.beta2 = (float)P.beta2; a.eps = (float)P.eps;
   a.clipping = (float)P.clipping; a.critic_coeff = (float)P.critic_coeff; a.entropy_bonus = (float)P.entropy_bonus;
+  a.E = P.n_trajectories;
+  a.member_keys = nullptr;
+  a.ws_stride = 0;
+  a.n_epochs = P.n_epochs;
+  a.member_hyper = nullptr;
+}
+
+hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStream_t st, int n_members, const uint64_t *member_keys,
+                                 const PpoMemberHyper *member_hyper) {
+  (void)hipGetLastError();
+  const int H = sh.rules_host.height, W = sh.rules_host.width, C = P.n_channels;
+  if (!ppo_cnn_shape_supported(H, W, C) || !pc_learner_ok(P)) return hipErrorInvalidValue;
+  if (n_members < 0 || n_members > 65535 || (n_members > 0 && P.n_trajectories % n_members != 0)) return hipErrorInvalidValue;  // (gridDim.y)
+  if (member_hyper && n_members < 1) return hipErrorInvalidValue;
+  PpoCnnArgs a;
+  pc_fill_args(a, sh, P);
   a.E = n_members > 0 ? P.n_trajectories / n_members : P.n_trajectories;
   a.member_keys = member_keys;
   a.ws_stride = ppo_cnn_members_stride_bytes(H, W, C, P.batch) / sizeof(float);
@@ -569,6 +631,23 @@ hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStr
   if (H == 7 && W == 8) SGK_PC_LAUNCH_C(7, 8);
   SGK_PC_LAUNCH_C(7, 9);
 #undef SGK_PC_LAUNCH_C
+}
+
+bool ppo_cnn_trans_shape_supported(int height, int width, int n_channels) {
+  return height == 5 && width == 5 && (n_channels == 4 || n_channels == 5 || n_channels == 8);  // the shapes sgk_convq_*_trans act on
+}
+
+hipError_t launch_ppo_cnn_epochs_trans(const Shard &sh, const PpoCnnLearner &P, const int8_t *prev_states, hipStream_t st) {
+  (void)hipGetLastError();
+  const int C = P.n_channels;
+  if (!ppo_cnn_trans_shape_supported(sh.rules_host.height, sh.rules_host.width, C) || !pc_learner_ok(P) || !prev_states)
+    return hipErrorInvalidValue;
+  PpoCnnTransArgs a;
+  pc_fill_args(a, sh, P);
+  a.prev_states = prev_states;
+  if (C == 5) return launch_ppo_cnn_shape<5, 5, 5, false, false, 2>(a, P.n_epochs, 1, st);
+  if (C == 4) return launch_ppo_cnn_shape<5, 5, 4, false, false, 2>(a, P.n_epochs, 1, st);
+  return launch_ppo_cnn_shape<5, 5, 8, false, false, 2>(a, P.n_epochs, 1, st);
 }
 
 }  // namespace sgk

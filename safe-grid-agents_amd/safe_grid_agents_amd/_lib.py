@@ -233,6 +233,8 @@ _SIGNATURES = {
     "sgk_ppo_epochs_members_hyper": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoLearner), ctypes.c_int32, _V, _V]),
     "sgk_ppo_cnn_epochs": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner)]),
     "sgk_ppo_cnn_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
+    "sgk_ppo_cnn_epochs_trans": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), _V]),
+    "sgk_ppo_cnn_trans_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32]),
     "sgk_ppo_cnn_epochs_members": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), ctypes.c_int32, _V]),
     "sgk_ppo_cnn_members_workspace_bytes": (ctypes.c_int64, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "sgk_ppo_cnn_epochs_members_hyper": (ctypes.c_int, [_V, ctypes.POINTER(SgkPpoCnnLearner), ctypes.c_int32, _V, _V]),

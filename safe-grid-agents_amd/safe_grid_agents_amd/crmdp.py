@@ -223,7 +223,8 @@ class BatchedPPOCRMDPAgent(BatchedPPOAgent):
 
     transitions=True (passed on to BatchedPPOAgent) is the PARITY path: the policy is the reference's two-channel PPOCNNAgent acting on
     [previous board, board] ([board, board] at a reset), gathered by sgk_convq_rollout_trans; it reproduces the reference's own run
-    (tests/test_gpu_transition_golden.py). The default (transitions=False) is NON-parity, labelled: the detector sees transitions, the
+    (tests/test_gpu_transition_golden.py); fused_transition_learn=True (passed on as well) makes its learn() sgk_ppo_cnn_epochs_trans
+    instead of the torch graph (tests/test_gpu_transition_learn.py). The default (transitions=False) is NON-parity, labelled: the detector sees transitions, the
     policy does not -- it acts on the current board (1 channel). The single-env PPOCRMDPAgent is the parity path for one env.
 
     on_unbounded: "raise" (default) -- stats() raises RuntimeError naming the first trajectory with a corrupt state that has no bound

@@ -1030,6 +1030,24 @@ class BatchedGridworldEnv:
         """Bytes of device workspace sgk_ppo_cnn_epochs needs on this level with n_channels and batch rows; SgkError when unsupported."""
         return self._workspace_bytes(self.lib.sgk_ppo_cnn_workspace_bytes, n_channels, batch)
 
+    def ppo_cnn_epochs_trans(self, learner, prev_states):
+        """ppo_cnn_epochs for the two-board body (sgk_ppo_cnn_epochs_trans): `learner` as there, with network.0.0.weight and
+        bottleneck.weight (and their Adam state and old-policy copies) twice the size; prev_states int8 [horizon, n_trajectories,
+        cells] on this device, the previous board of every row beside the learner's `states` (None: passed on as NULL, which the
+        call refuses)."""
+        pp = None
+        if prev_states is not None:
+            shape = (int(learner.horizon), int(learner.n_trajectories), self.n_cells)
+            pp = ctypes.c_void_p(self._check(prev_states, "prev_states", shape=shape, dtypes=("int8",)).data_ptr())
+        self._sync_torch_to_lib()
+        _lib.check(self.lib.sgk_ppo_cnn_epochs_trans(self._h.ptr, ctypes.byref(learner), pp))
+        self._sync_lib_to_torch()
+
+    def ppo_cnn_trans_workspace_bytes(self, n_channels, batch):
+        """Bytes of device workspace sgk_ppo_cnn_epochs_trans needs on this level with n_channels and batch rows; SgkError when
+        unsupported."""
+        return self._workspace_bytes(self.lib.sgk_ppo_cnn_trans_workspace_bytes, n_channels, batch)
+
     def _member_convq_weights(self, weights, n_members, n_channels, n_layers):
         """sgk_convq_weights addressing member 0 of float32 device tensors stacked on a leading member axis: w1 [M, C, 1, 3, 3], b1
         [M, C], w2 [M, C, C, 3, 3], b2, wb [M, C, 1, 1, 1], bb, wh [M, C, C, 3, 3], bh, wl [M, 4, C * cells], bl [M, 4]."""

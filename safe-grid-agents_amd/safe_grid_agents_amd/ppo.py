@@ -243,14 +243,18 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
 
     learn() is one launch for the ppo-mlp shapes above with 2 <= batch_size <= 64 (sgk_ppo_epochs); with fused_conv_learn=True
     (off by default) the ppo-cnn shapes with 2 <= batch_size <= 64 learn on the device as well (sgk_ppo_cnn_epochs: three launches
-    per epoch); every other case runs torch autograd.
+    per epoch), the two-channel body below with fused_transition_learn=True (sgk_ppo_cnn_epochs_trans); every other case runs
+    torch autograd.
 
     transitions=True (ppo-cnn on BoatRace's 5 x 5 board; the reference's `trans-boat` agents): the policy acts on the observation of
     TransitionBoatRace, [previous board, board] -- [board, board] at a reset -- through the two-channel kernels (sgk_convq_sample_trans,
     sgk_convq_act_trans, sgk_convq_rollout_trans). `net` is then a PPOCNNAgent with two input channels, the agent owns `prev_boards`
     (int8 [N, cells]: what the last fused rollout left, the previous boards of the observation the next action is chosen on; a caller
     that steps the env itself copies the boards there before each step), the rollout carries `prev_states` beside `states`, and
-    learn() is the torch path (the fused conv learner has one input channel). Without the fused conv kernel there is no such form.
+    learn() is the torch path unless fused_transition_learn=True (off by default): then, with 2 <= batch_size <= 64, it is
+    sgk_ppo_cnn_epochs_trans, the fused conv learner with two input planes (three launches per epoch; `fused_learn` tells which path
+    runs). fused_conv_learn=True stays refused with transitions=True (sgk_ppo_cnn_epochs has one input channel), and
+    fused_transition_learn=True without transitions=True is refused. Without the fused conv kernel there is no such form.
 
     The action stream comes from the counter RNG (keyed by global env index and the agent's draw counter), so it does not
     depend on how the envs are sharded over GPUs. `net` is a PPOMLPAgent / PPOCNNAgent on the env's device: its
@@ -258,7 +262,8 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
 
     reads_boards = True  # acts on the materialised cells (batched_default_eval must keep writing them)
 
-    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True, fused_conv_learn=False, transitions=False):
+    def __init__(self, env, args, body="mlp", graph_epochs=True, fused_conv=True, fused_conv_learn=False, transitions=False,
+                 fused_transition_learn=False):
         import types
 
         cfg = types.SimpleNamespace(**vars(args))
@@ -272,10 +277,13 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             if body != "cnn":
                 raise ValueError("transitions=True is the two-channel conv body: body must be 'cnn'")
             if fused_conv_learn:
-                raise ValueError("fused_conv_learn=True with transitions=True: sgk_ppo_cnn_epochs has one input channel; learn() is the torch path")
+                raise ValueError("fused_conv_learn=True with transitions=True: sgk_ppo_cnn_epochs has one input channel; the two-channel "
+                                 "learner is fused_transition_learn=True (sgk_ppo_cnn_epochs_trans)")
             # the observation space of TransitionBoatRace, (2, H, W), for the network alone: env.observation_space stays (1, H, W)
             hw = tuple(int(v) for v in env.observation_space.shape[-2:])
             net_env = types.SimpleNamespace(action_space=env.action_space, observation_space=types.SimpleNamespace(shape=(2,) + hw))
+        elif fused_transition_learn:
+            raise ValueError("fused_transition_learn=True is the learner of the two-channel body: it needs transitions=True")
         self.net = (PPOMLPAgent if body == "mlp" else PPOCNNAgent)(net_env, cfg)
         self.discount = float(args.discount)
         self.epochs, self.batch_size = int(args.epochs), int(args.batch_size)
@@ -325,7 +333,8 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             self._cw_old, self._cw = self._conv_weights(self.net.old_policy), self._conv_weights(self.net)
             self.graph_gather = False  # four launches per step: calling them costs less than a graph replay's fixed share (33.6 vs 35.7 us)
         # ppo-cnn's learn() on the device (sgk_ppo_cnn_epochs) where that kernel applies; Adam's state and its workspace then live in self._pl
-        if bool(fused_conv_learn) and self.fused_conv and 2 <= self.batch_size <= 64:
+        # (transitions=True: sgk_ppo_cnn_epochs_trans, asked for by its own keyword)
+        if bool(fused_transition_learn if self.transitions else fused_conv_learn) and self.fused_conv and 2 <= self.batch_size <= 64:
             self.fused_learn = True
 
     @staticmethod
@@ -575,9 +584,12 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         """`epochs` updates of the conv body by sgk_ppo_cnn_epochs: sampling, both forwards, loss, backward and Adam of every epoch
         on the device, three launches per epoch. The kernels read and update the torch parameters in place and read the old
         policy's in place; Adam's state, the step counter and the workspace are allocated once (fixed addresses: the call can be
-        recorded in a graph when `rows` is None)."""
+        recorded in a graph when `rows` is None). transitions=True: sgk_ppo_cnn_epochs_trans with the rollout's prev_states."""
         L, keep = self._cnn_learner(rollout, rows, rows_out)
-        self.env.ppo_cnn_epochs(L)
+        if self.transitions:
+            self.env.ppo_cnn_epochs_trans(L, rollout.prev_states)
+        else:
+            self.env.ppo_cnn_epochs(L)
         return keep
 
     def _cnn_learner(self, rollout, rows=None, rows_out=None):
@@ -590,8 +602,9 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         cur, old = dict(self.net.named_parameters()), dict(self.net.old_policy.named_parameters())
         own = [cur[k].data for k in self.CNN_PARAMS]
         olds = [old[k].data for k in self.CNN_PARAMS[:10]]
+        ws_bytes = self.env.ppo_cnn_trans_workspace_bytes if self.transitions else self.env.ppo_cnn_workspace_bytes
         if self._pl is None:
-            nbytes = self.env.ppo_cnn_workspace_bytes(self.n_channels, self.batch_size)
+            nbytes = ws_bytes(self.n_channels, self.batch_size)
             self._pl = {"m": [torch.zeros_like(p) for p in own], "v": [torch.zeros_like(p) for p in own],
                         "step": torch.zeros(1, dtype=torch.int64, device=self.device),
                         "ws": torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
@@ -606,8 +619,8 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
         chk(rollout.lengths, "rollout.lengths", shape=(n,), dtypes=("int32",))
         L.states, L.actions, L.returns, L.lengths = ptr(rollout.states), ptr(rollout.actions), ptr(rollout.returns), ptr(rollout.lengths)
         L.horizon, L.n_channels, L.batch, L.n_epochs, L.n_trajectories = T, self.n_channels, self.batch_size, self.epochs, n
-        C, cells = self.n_channels, self.env.n_cells
-        sizes = (9 * C, C, 9 * C * C, C, C, C, 9 * C * C, C, 4 * C * cells, 4, 9 * C * C, C, C * cells, 1)  # what the kernels index
+        C, cells, cin = self.n_channels, self.env.n_cells, 2 if self.transitions else 1  # (two planes: 18 C and 2 C floats)
+        sizes = (9 * C * cin, C, 9 * C * C, C, C * cin, C, 9 * C * C, C, 4 * C * cells, 4, 9 * C * C, C, C * cells, 1)  # what the kernels index
         for i, k in enumerate(self.CNN_PARAMS):
             chk(own[i], "parameter " + k, numel=sizes[i], dtypes=("float32",))
             chk(pl["m"][i], "Adam exp_avg of " + k, numel=sizes[i], dtypes=("float32",))
@@ -618,7 +631,7 @@ class BatchedPPOAgent(BaseActor, BaseLearner, BaseExplorer):
             L.old_params[i] = olds[i].data_ptr()
         chk(pl["step"], "step", shape=(1,), dtypes=("int64",))
         chk(self._stats, "stats", shape=(self.epochs, 3), dtypes=("float32",))
-        chk(pl["ws"], "workspace", numel=self.env.ppo_cnn_workspace_bytes(self.n_channels, self.batch_size), dtypes=("uint8",))
+        chk(pl["ws"], "workspace", numel=ws_bytes(self.n_channels, self.batch_size), dtypes=("uint8",))
         L.step, L.stats_out, L.workspace = ptr(pl["step"]), ptr(self._stats), ptr(pl["ws"])
         keep = self._flat_rows(rollout, rows, rows_out)
         if keep is not None:

@@ -103,6 +103,10 @@ _HASH_GROW = ("hash-grow", "HG", dict(action="store_true", default=argparse.SUPP
 # acting on [previous board, board] as TransitionBoatRace shows it (BatchedPPOAgent(transitions=True): the parity form). Absent unless
 # given; another level stops the run with a message (check_transition_policy)
 _TRANSITION_POLICY = ("transition-policy", "TP", dict(action="store_true", default=argparse.SUPPRESS))
+# extension, beside --transition-policy: `--fused-transition-learn` makes that body's learn() the fused HIP learner
+# (sgk_ppo_cnn_epochs_trans; BatchedPPOAgent(fused_transition_learn=True)) instead of the torch graph. Absent unless given; without
+# --transition-policy it stops the run with a message (check_fused_transition_learn)
+_FUSED_TRANSITION_LEARN = ("fused-transition-learn", "FTL", dict(action="store_true", default=argparse.SUPPRESS))
 _AGENT_FLAGS = {
     "random": [],
     "single": [("action", "a", dict(type=int, default=0))],
@@ -123,9 +127,9 @@ _AGENT_FLAGS = {
                _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
     "ppo-mlp": _PPO_FLAGS + [("n-hidden", "hd", dict(type=int, default=100)), _DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE] + _PBT,
     "ppo-cnn": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _MEMBERS, _SWEEP, _ENSEMBLE,
-                                                                         _TRANSITION_POLICY] + _PBT,
+                                                                         _TRANSITION_POLICY, _FUSED_TRANSITION_LEARN] + _PBT,
     # the reference's flags (agent_parser_configs.yaml:124-135) and no more: one agent, no population of it
-    "ppo-crmdp": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _TRANSITION_POLICY],
+    "ppo-crmdp": [("n-channels", "ch", dict(type=int, default=5))] + _PPO_FLAGS + [_DEVICE, _GRADLOG, _TRANSITION_POLICY, _FUSED_TRANSITION_LEARN],
 }
 
 
@@ -246,6 +250,9 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         consensus = {"hashed": True}
     hash_grow = check_hash_grow(args)  # --hash-grow: True / False; SystemExit on a level whose tables are not hashed
     transitions = check_transition_policy(args)  # --transition-policy: True / False; SystemExit off trans-boat or with --members
+    trans_kw = {"transitions": True} if transitions else {}
+    if check_fused_transition_learn(args):  # --fused-transition-learn: SystemExit without --transition-policy
+        trans_kw["fused_transition_learn"] = True
 
     rank, local_rank, world = sdist.env_from_torchrun()
     if consensus is not None and world > 1:
@@ -289,14 +296,14 @@ def train_batched(args, writer_factory=None, reporter=_noop):
         import torch
 
         torch.manual_seed(args.seed or 0)
-        agent = BatchedPPOAgent(env, args, body=args.agent_alias[4:], **({"transitions": True} if transitions else {}))
+        agent = BatchedPPOAgent(env, args, body=args.agent_alias[4:], **trans_kw)
     elif args.agent_alias == "ppo-crmdp":  # ppo-cnn with the corrupt-reward filter between the gather and the returns (crmdp.py)
         import torch
 
         from .crmdp import BatchedPPOCRMDPAgent
 
         torch.manual_seed(args.seed or 0)
-        agent = BatchedPPOCRMDPAgent(env, args, **({"transitions": True} if transitions else {}))
+        agent = BatchedPPOCRMDPAgent(env, args, **trans_kw)
     elif args.agent_alias == "deep-q":
         import torch
 
@@ -429,6 +436,16 @@ def check_transition_policy(args):
         raise SystemExit("--transition-policy runs on trans-boat only: %s observes one board, not a transition" % (args.env_alias,))
     if int(getattr(args, "members", 0) or 0):
         raise SystemExit("--transition-policy has no population form: drop --members")
+    return True
+
+
+def check_fused_transition_learn(args):
+    """--fused-transition-learn of `args` -> True / False. SystemExit with a plain message without --transition-policy: the flag
+    chooses the learner of that body (check_transition_policy has the body's own conditions)."""
+    if not getattr(args, "fused_transition_learn", False):
+        return False
+    if not getattr(args, "transition_policy", False):
+        raise SystemExit("--fused-transition-learn is the fused learner of the two-channel body: give --transition-policy as well")
     return True
 
 
