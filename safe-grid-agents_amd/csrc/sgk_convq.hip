@@ -1,5 +1,6 @@
 // sgk_convq.hip -- the reference's convolutional body, forward + draw for every env in ONE launch (sgk_convq_sample, sgk_convq_act; sgk_convq_act_members_all: n_members
-// stacked bodies x every env).
+// stacked bodies x every env; sgk_convq_sample_trans, sgk_convq_act_trans: the observation [previous board, board]). ONE kernel template,
+// convq_act_kernel<H, W, C, MEMBERS, CI>, and one launch sequence, convq_act_launch, for all of them.
 //
 // The network is PPOCNNAgent's (policy_cnn.py:17-81) trunk and ONE four-way head:
 //     trunk = relu(conv3x3(relu(conv3x3(x, 1 -> C)), C -> C)) + conv1x1(x, 1 -> C)          (n_layers = 2, the reference's default)
@@ -53,14 +54,22 @@ namespace sgk {
 // greedy: select_action's first maximum with a draw that is never below epsilon 0, no Philox block; mode, eps, seed, env_base, draw and
 // the two device scalars are not read. Everything else is the same code, so member m's scores and actions are the bytes the
 // MEMBERS = false kernel leaves for member m's slices and epsilon 0.
-template <int HH, int WW, int C, bool MEMBERS = false>
+//
+// CI = 2 (sgk_convq_act_trans / sgk_convq_sample_trans): the same forward on the observation of a transition env, [previous board,
+// board] (ConvQGeom's CI = 2: w1 [C][2][3][3], wb [C][2][1][1]). One difference: a lane requests its bytes of BOTH boards for the next
+// pass -- the current one from the env's own boards (`pitch`), the previous one from `prev`, the caller's dense int8 [n][NC] array;
+// null = the current board twice (no env has stepped since its reset) -- and writes them to planes 1 and 0. `prev` is the LAST argument
+// and CI = 1 never reads it: the one-board kernels are the instruction streams they were before it existed, but for the offset of
+// the hidden arguments behind it (profiles/convq_one_kernel/resource_usage.log). No member form.
+template <int HH, int WW, int C, bool MEMBERS = false, int CI = 1>
 __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
     const int8_t *__restrict__ boards, int pitch, const float *__restrict__ w1r, const float *__restrict__ b1r, const float *__restrict__ w2r,
     const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr, const float *__restrict__ whr,
     const float *__restrict__ bhr, const float *__restrict__ wlr, const float *__restrict__ blr, uint8_t *__restrict__ actions,
     float *__restrict__ scores_out, int64_t n, int mode, double eps, uint64_t seed, uint64_t env_base, uint64_t draw,
-    const double *__restrict__ eps_ptr, const uint64_t *__restrict__ draw_ptr) {
-  typedef ConvQGeom<HH, WW, C> G;
+    const double *__restrict__ eps_ptr, const uint64_t *__restrict__ draw_ptr, const int8_t *__restrict__ prev) {
+  static_assert(!(MEMBERS && CI == 2), "the two-board kernel has no member form");
+  typedef ConvQGeom<HH, WW, C, CI> G;
   extern __shared__ __attribute__((aligned(16))) unsigned char convq_smem[];
   float *Lf = reinterpret_cast<float *>(convq_smem);
   float *WL = Lf + G::O_WL, *act = Lf + G::O_ACT;
@@ -78,9 +87,9 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
   }
   CqLane<G> L;
   cq_setup<G, WW, C>(L, WL, act, w1r, w2r, whr, wlr);
-  // ---- this lane's board bytes of a pass ----
+  // ---- this lane's board bytes of a pass: element i = t + CQ_WG * u = (env e, cell pos) ----
   int b_lds[G::NB], b_env[G::NB], b_goff[G::NB];
-  int8_t cur[G::NB];
+  int8_t cur[G::NB], prv[G::NB];  // (prv: CI = 2 only)
 #pragma unroll
   for (int u = 0; u < G::NB; ++u) {
     const int i = t + CQ_WG * u;
@@ -90,7 +99,7 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
     b_env[u] = live ? e : 0x7fffffff;
     b_goff[u] = e * pitch + pos;
     b_lds[u] = e * G::ENV_F + G::CENTRE + y * G::PW + x;
-    cur[u] = 0;
+    cur[u] = prv[u] = 0;
   }
   const int64_t n_pass = (n + G::ENVS - 1) / G::ENVS;
   auto request_boards = [&](int64_t pass) {
@@ -99,16 +108,25 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
     const int lim = left < G::ENVS ? (int)left : G::ENVS;
 #pragma unroll
     for (int u = 0; u < G::NB; ++u) cur[u] = b_env[u] < lim ? src[b_goff[u]] : (int8_t)0;
+    if constexpr (CI == 2) {
+      const int8_t *psrc = prev ? prev + pass * G::ENVS * (int64_t)G::NC : nullptr;
+#pragma unroll
+      for (int u = 0; u < G::NB; ++u)
+        prv[u] = !psrc ? cur[u] : b_env[u] < lim ? psrc[t + CQ_WG * u] : (int8_t)0;  // (e < lim: element i lies inside [n][NC])
+    }
   };
   if ((int64_t)blockIdx.x < n_pass) request_boards(blockIdx.x);
   __syncthreads();
   for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
     const int64_t env0 = pass * G::ENVS;
     const int hz = (int)(pass >> 44);  // (always 0: see cq_network)
-    // ---- the boards -> plane 0 (float); the next pass's bytes requested ----
+    // ---- the board -> plane 0 (float; CI = 2: previous -> plane 0, current -> plane 1); the next pass's bytes requested ----
 #pragma unroll
     for (int u = 0; u < G::NB; ++u)
-      if (b_env[u] < G::ENVS) act[b_lds[u]] = (float)cur[u];
+      if (b_env[u] < G::ENVS) {
+        if constexpr (CI == 2) act[b_lds[u]] = (float)prv[u];
+        act[b_lds[u] + (CI - 1) * G::PL] = (float)cur[u];
+      }
     if (pass + gridDim.x < n_pass) request_boards(pass + gridDim.x);
     __syncthreads();
     cq_network<G, C>(L, act, WL, hz, w1r, b1r, w2r, b2r, wbr, bbr, whr, bhr);
@@ -133,202 +151,55 @@ __global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_kernel(
         }
       }
     }
-    // (the next pass writes plane 0 first and passes a barrier before planes 1 .. C are written again)
+    // (the next pass writes the input planes first and passes a barrier before the planes behind them are written again; CI = 2: wave 0
+    // sums the products in planes 2 .. 5 meanwhile, which is why they are not left in plane 1 ..)
   }
+}
+
+// One launch of convq_act_kernel<H, W, C, MEMBERS, CI> for the listed board shape and channel count of this shard. The grid: one workgroup
+// per pass while they fit the chip; MEMBERS: (a member's workgroups, n_members) -- one per pass while all members' fit the chip (one
+// member: the single kernel's grid), at least one: the members rollout's rule (launch_convq_rollout) with the same per_cu.
+template <bool MEMBERS, int CI, class Boards>
+static hipError_t convq_act_launch(Boards boards, const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, int mode,
+                                   const int8_t *prev_boards, uint8_t *actions, float *scores, double eps, uint64_t draw, const double *eps_dev,
+                                   const uint64_t *draw_dev, hipStream_t st) {
+  (void)hipGetLastError();
+  return cq_dispatch(boards, sh.rules_host.height, sh.rules_host.width, n_channels, [&](auto board, auto channels) {
+    constexpr int HV = decltype(board)::H, WV = decltype(board)::W, CV = decltype(channels)::value;
+    typedef ConvQGeom<HV, WV, CV, CI> G;
+    constexpr size_t lds = G::lds_bytes;
+    static_assert(lds <= 160u * 1024u, "convq LDS plan");
+    const int64_t n_pass = (sh.n + G::ENVS - 1) / G::ENVS;
+    hipError_t ae = allow_dynamic_lds<convq_act_kernel<HV, WV, CV, MEMBERS, CI>>(sh.device, (int)lds);
+    if (ae != hipSuccess) return ae;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));
+    const dim3 grid = MEMBERS ? dim3(grid_for(n_pass, std::max(sh.n_cus * per_cu / n_members, 1)), n_members) : dim3(grid_for(n_pass, sh.n_cus * per_cu));
+    convq_act_kernel<HV, WV, CV, MEMBERS, CI><<<grid, dim3(CQ_WG), lds, st>>>(sh.boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl,
+                                                                             w.bl, actions, scores, sh.n, mode, eps, sh.seed, sh.env_base, draw,
+                                                                             eps_dev, draw_dev, prev_boards);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, uint8_t *actions, float *scores, double eps, uint64_t draw,
                             const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
-  (void)hipGetLastError();
-  const int H = sh.rules_host.height, W = sh.rules_host.width;
-#define SGK_CONVQ_LAUNCH(HV, WV, CV)                                                                                       \
-  do {                                                                                                                     \
-    constexpr size_t lds = ConvQGeom<HV, WV, CV>::lds_bytes;                                                               \
-    const int64_t n_pass = (sh.n + ConvQGeom<HV, WV, CV>::ENVS - 1) / ConvQGeom<HV, WV, CV>::ENVS;                                                               \
-    static_assert(lds <= 160u * 1024u, "convq LDS plan");                                                                 \
-    hipError_t ae = allow_dynamic_lds<convq_act_kernel<HV, WV, CV>>(sh.device, (int)lds);                                  \
-    if (ae != hipSuccess) return ae;                                                                                       \
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                                \
-    const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
-    convq_act_kernel<HV, WV, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(sh.boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, \
-                                                                       w.wl, w.bl, actions, scores, sh.n, mode, eps, sh.seed, \
-                                                                       sh.env_base, draw, eps_dev, draw_dev);              \
-  } while (0)
-#define SGK_CONVQ_LAUNCH_C(HV, WV)                                                                                         \
-  do {                                                                                                                     \
-    if (n_channels == 5) SGK_CONVQ_LAUNCH(HV, WV, 5);                                                                      \
-    else if (n_channels == 4) SGK_CONVQ_LAUNCH(HV, WV, 4);                                                                 \
-    else if (n_channels == 8) SGK_CONVQ_LAUNCH(HV, WV, 8);                                                                 \
-    else return hipErrorInvalidValue;                                                                                      \
-  } while (0)
-  if (H == 5 && W == 5) SGK_CONVQ_LAUNCH_C(5, 5);
-  else if (H == 6 && W == 5) SGK_CONVQ_LAUNCH_C(6, 5);
-  else if (H == 6 && W == 6) SGK_CONVQ_LAUNCH_C(6, 6);
-  else if (H == 6 && W == 8) SGK_CONVQ_LAUNCH_C(6, 8);
-  else if (H == 7 && W == 7) SGK_CONVQ_LAUNCH_C(7, 7);
-  else if (H == 7 && W == 8) SGK_CONVQ_LAUNCH_C(7, 8);
-  else if (H == 7 && W == 9) SGK_CONVQ_LAUNCH_C(7, 9);
-  else return hipErrorInvalidValue;
-#undef SGK_CONVQ_LAUNCH_C
-#undef SGK_CONVQ_LAUNCH
-  return hipGetLastError();
+  return convq_act_launch<false, 1>(CqOneBoardShapes{}, sh, w, n_channels, 1, mode, nullptr, actions, scores, eps, draw, eps_dev, draw_dev, st);
 }
 
-// the member instantiation: a member's workgroups are one per pass while all members' fit the chip (one member: the single kernel's
-// grid), at least one -- the members rollout's rule (launch_convq_rollout) with the single launcher's per_cu
+// (the member kernel reads neither the mode nor the draw's arguments)
 hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, uint8_t *member_actions,
                                     float *member_scores, hipStream_t st) {
-  (void)hipGetLastError();
   if (n_members < 1 || n_members > SGK_MEMBERS_MAX) return hipErrorInvalidValue;
-  const int H = sh.rules_host.height, W = sh.rules_host.width;
-#define SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, CV)                                                                               \
-  do {                                                                                                                     \
-    constexpr size_t lds = ConvQGeom<HV, WV, CV>::lds_bytes;                                                               \
-    const int64_t n_pass = (sh.n + ConvQGeom<HV, WV, CV>::ENVS - 1) / ConvQGeom<HV, WV, CV>::ENVS;                         \
-    hipError_t ae = allow_dynamic_lds<convq_act_kernel<HV, WV, CV, true>>(sh.device, (int)lds);                            \
-    if (ae != hipSuccess) return ae;                                                                                       \
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                 \
-    const int member_wgs = grid_for(n_pass, std::max(sh.n_cus * per_cu / n_members, 1));                                   \
-    convq_act_kernel<HV, WV, CV, true><<<dim3(member_wgs, n_members), dim3(CQ_WG), lds, st>>>(                             \
-        sh.boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl, member_actions, member_scores, sh.n, 0, 0.0, 0, 0, 0, \
-        nullptr, nullptr);                                                                                                 \
-  } while (0)
-#define SGK_CONVQ_MEMBERS_LAUNCH_C(HV, WV)                                                                                 \
-  do {                                                                                                                     \
-    if (n_channels == 5) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 5);                                                              \
-    else if (n_channels == 4) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 4);                                                         \
-    else if (n_channels == 8) SGK_CONVQ_MEMBERS_LAUNCH(HV, WV, 8);                                                         \
-    else return hipErrorInvalidValue;                                                                                      \
-  } while (0)
-  if (H == 5 && W == 5) SGK_CONVQ_MEMBERS_LAUNCH_C(5, 5);
-  else if (H == 6 && W == 5) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 5);
-  else if (H == 6 && W == 6) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 6);
-  else if (H == 6 && W == 8) SGK_CONVQ_MEMBERS_LAUNCH_C(6, 8);
-  else if (H == 7 && W == 7) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 7);
-  else if (H == 7 && W == 8) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 8);
-  else if (H == 7 && W == 9) SGK_CONVQ_MEMBERS_LAUNCH_C(7, 9);
-  else return hipErrorInvalidValue;
-#undef SGK_CONVQ_MEMBERS_LAUNCH_C
-#undef SGK_CONVQ_MEMBERS_LAUNCH
-  return hipGetLastError();
+  return convq_act_launch<true, 1>(CqOneBoardShapes{}, sh, w, n_channels, n_members, 0, nullptr, member_actions, member_scores, 0.0, 0, nullptr,
+                                   nullptr, st);
 }
 
-// sgk_convq_act_trans / sgk_convq_sample_trans: the same forward on the observation of a transition env, [previous board, board]
-// (ConvQGeom's CI = 2: w1 [C][2][3][3], wb [C][2][1][1]). convq_act_kernel's pass loop with one difference: a lane requests its bytes of
-// BOTH boards for the next pass -- the current one from the env's own boards (`pitch`), the previous one from `prev`, the caller's dense
-// int8 [n][NC] array; null = the current board twice (no env has stepped since its reset) -- and writes them to planes 1 and 0. A
-// kernel of its own, so that convq_act_kernel stays the instruction stream it was. No member form.
-template <int HH, int WW, int C>
-__global__ __launch_bounds__(CQ_WG, CQ_WAVES_FOR(C)) void convq_act_trans_kernel(
-    const int8_t *__restrict__ boards, const int8_t *__restrict__ prev, int pitch, const float *__restrict__ w1r, const float *__restrict__ b1r,
-    const float *__restrict__ w2r, const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr,
-    const float *__restrict__ whr, const float *__restrict__ bhr, const float *__restrict__ wlr, const float *__restrict__ blr,
-    uint8_t *__restrict__ actions, float *__restrict__ scores_out, int64_t n, int mode, double eps, uint64_t seed, uint64_t env_base,
-    uint64_t draw, const double *__restrict__ eps_ptr, const uint64_t *__restrict__ draw_ptr) {
-  typedef ConvQGeom<HH, WW, C, 2> G;
-  extern __shared__ __attribute__((aligned(16))) unsigned char convq_smem[];
-  float *Lf = reinterpret_cast<float *>(convq_smem);
-  float *WL = Lf + G::O_WL, *act = Lf + G::O_ACT;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (eps_ptr) eps = *eps_ptr;
-  if (draw_ptr) draw = *draw_ptr;
-  CqLane<G> L;
-  cq_setup<G, WW, C>(L, WL, act, w1r, w2r, whr, wlr);
-  // ---- this lane's board bytes of a pass: element i = t + CQ_WG * u = (env e, cell pos) ----
-  int b_lds[G::NB], b_env[G::NB], b_goff[G::NB];
-  int8_t cur[G::NB], prv[G::NB];
-#pragma unroll
-  for (int u = 0; u < G::NB; ++u) {
-    const int i = t + CQ_WG * u;
-    const bool live = i < G::ENVS * G::NC;
-    const int e = live ? i / G::NC : 0, pos = live ? i - e * G::NC : 0;
-    const int y = pos / WW, x = pos - y * WW;
-    b_env[u] = live ? e : 0x7fffffff;
-    b_goff[u] = e * pitch + pos;
-    b_lds[u] = e * G::ENV_F + G::CENTRE + y * G::PW + x;
-    cur[u] = prv[u] = 0;
-  }
-  const int64_t n_pass = (n + G::ENVS - 1) / G::ENVS;
-  auto request_boards = [&](int64_t pass) {
-    const int8_t *src = boards + pass * G::ENVS * (int64_t)pitch;  // (uniform)
-    const int8_t *psrc = prev ? prev + pass * G::ENVS * (int64_t)G::NC : nullptr;
-    const int64_t left = n - pass * G::ENVS;
-    const int lim = left < G::ENVS ? (int)left : G::ENVS;
-#pragma unroll
-    for (int u = 0; u < G::NB; ++u) {
-      cur[u] = b_env[u] < lim ? src[b_goff[u]] : (int8_t)0;
-      prv[u] = !psrc ? cur[u] : b_env[u] < lim ? psrc[t + CQ_WG * u] : (int8_t)0;  // (e < lim: element i lies inside [n][NC])
-    }
-  };
-  if ((int64_t)blockIdx.x < n_pass) request_boards(blockIdx.x);
-  __syncthreads();
-  for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-    const int64_t env0 = pass * G::ENVS;
-    const int hz = (int)(pass >> 44);  // (always 0: see cq_network)
-    // ---- previous -> plane 0, current -> plane 1 (float); the next pass's bytes requested ----
-#pragma unroll
-    for (int u = 0; u < G::NB; ++u)
-      if (b_env[u] < G::ENVS) {
-        act[b_lds[u]] = (float)prv[u];
-        act[b_lds[u] + G::PL] = (float)cur[u];
-      }
-    if (pass + gridDim.x < n_pass) request_boards(pass + gridDim.x);
-    __syncthreads();
-    cq_network<G, C>(L, act, WL, hz, w1r, b1r, w2r, b2r, wbr, bbr, whr, bhr);
-    if (wave == 0) {
-      constexpr int NIT = (G::ENVS * 4 + 63) / 64;
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int idx = it * 64 + lane;
-        float q0, q1, q2, q3;
-        cq_outputs<G>(act, blr, idx, q0, q1, q2, q3);
-        const int64_t env = env0 + (idx >> 2);
-        if (idx < G::ENVS * 4 && (idx & 3) == 0 && env < n) {
-          actions[env] = (uint8_t)(mode == 0 ? pick_action<0>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps)
-                                             : pick_action<1>(q0, q1, q2, q3, env_base + (uint64_t)env, draw, seed, eps));
-          if (scores_out) *reinterpret_cast<float4 *>(scores_out + 4 * env) = make_float4(q0, q1, q2, q3);
-        }
-      }
-    }
-    // (the next pass writes planes 0 and 1 first and passes a barrier before the planes behind them are written again: wave 0 sums
-    // the products in planes 2 .. 5 meanwhile, which is why they are not left in plane 1 ..)
-  }
-}
-
-// the two-plane kernel exists for the 5 x 5 board (BoatRace, the level TransitionBoatRace wraps); another level is a dispatch line
 hipError_t launch_convq_act_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, const int8_t *prev_boards, uint8_t *actions,
                                   float *scores, double eps, uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
-  (void)hipGetLastError();
-#define SGK_CONVQ_TRANS_LAUNCH(HV, WV, CV)                                                                                 \
-  do {                                                                                                                     \
-    typedef ConvQGeom<HV, WV, CV, 2> G2;                                                                                   \
-    constexpr size_t lds = G2::lds_bytes;                                                                                  \
-    static_assert(lds <= 160u * 1024u, "convq LDS plan");                                                                 \
-    const int64_t n_pass = (sh.n + G2::ENVS - 1) / G2::ENVS;                                                               \
-    hipError_t ae = allow_dynamic_lds<convq_act_trans_kernel<HV, WV, CV>>(sh.device, (int)lds);                            \
-    if (ae != hipSuccess) return ae;                                                                                       \
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_WAVES_FOR(CV), (160u * 1024u) / lds));                 \
-    const int grid = grid_for(n_pass, sh.n_cus * per_cu);                                                                  \
-    convq_act_trans_kernel<HV, WV, CV><<<dim3(grid), dim3(CQ_WG), lds, st>>>(                                              \
-        sh.boards, prev_boards, sh.pitch, w.w1, w.b1, w.w2, w.b2, w.wb, w.bb, w.wh, w.bh, w.wl, w.bl, actions, scores, sh.n, mode, eps, sh.seed, \
-        sh.env_base, draw, eps_dev, draw_dev);                                                                             \
-  } while (0)
-  if (!convq_trans_board_has_kernel(sh.rules_host.height, sh.rules_host.width)) return hipErrorInvalidValue;
-  if (n_channels == 5) SGK_CONVQ_TRANS_LAUNCH(5, 5, 5);
-  else if (n_channels == 4) SGK_CONVQ_TRANS_LAUNCH(5, 5, 4);
-  else if (n_channels == 8) SGK_CONVQ_TRANS_LAUNCH(5, 5, 8);
-  else return hipErrorInvalidValue;
-#undef SGK_CONVQ_TRANS_LAUNCH
-  return hipGetLastError();
+  return convq_act_launch<false, 2>(CqTwoBoardShapes{}, sh, w, n_channels, 1, mode, prev_boards, actions, scores, eps, draw, eps_dev, draw_dev, st);
 }
 
-bool convq_trans_board_has_kernel(int height, int width) { return height == 5 && width == 5; }
-
-bool convq_board_has_kernel(int height, int width) {
-  const int boards[][2] = {{5, 5}, {6, 5}, {6, 6}, {6, 8}, {7, 7}, {7, 8}, {7, 9}};
-  for (const auto &b : boards)
-    if (b[0] == height && b[1] == width) return true;
-  return false;
-}
+bool convq_board_has_kernel(int height, int width) { return cq_board_listed(CqOneBoardShapes{}, height, width); }
+bool convq_trans_board_has_kernel(int height, int width) { return cq_board_listed(CqTwoBoardShapes{}, height, width); }
 
 }  // namespace sgk

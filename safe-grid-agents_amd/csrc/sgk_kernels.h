@@ -114,14 +114,15 @@ hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channe
 // member_scores [n_members][n][4] or null
 hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, uint8_t *member_actions,
                                     float *member_scores, hipStream_t st);
-bool convq_board_has_kernel(int height, int width);  // the board shapes launch_convq_act dispatches
+bool convq_board_has_kernel(int height, int width);  // the board shapes launch_convq_act dispatches (sgk_convq.h's CqOneBoardShapes)
 // n_steps of {conv forward, draw, env.step} in one launch (sgk_convq_rollout.hip); outputs as for launch_policy_rollout.
 // n_members >= 1 (sgk_convq_rollout_members; 0: sgk_convq_rollout's own kernel): `w` addresses member 0 of the ten weight tensors stacked
 // [n_members][...], member m acts in the envs m * n / n_members ..; member_metrics as for launch_policy_rollout
 hipError_t launch_convq_rollout(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0, int32_t n_steps,
                                 uint32_t flags, int8_t *states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st,
                                 int n_members = 0, int64_t *member_metrics = nullptr);
-// the same two launches on the observation of a transition env, [previous board, board] (sgk_convq_*_trans): w.w1 is [C][2][3][3] and
+// the same two launches on the observation of a transition env, [previous board, board] (sgk_convq_*_trans; the CI = 2 instantiations of
+// convq_act_kernel and convq_rollout_kernel, launched by the same code as the one-board ones): w.w1 is [C][2][3][3] and
 // w.wb [C][2][1][1]; prev_boards: dense int8 [n][n_cells] (acting: read, null = the current board twice; rollout: read at entry unless
 // `fresh`, written at exit, never null); prev_states_out: channel 0 beside states_out's channel 1, or null
 hipError_t launch_convq_act_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, const int8_t *prev_boards, uint8_t *actions,
@@ -129,7 +130,7 @@ hipError_t launch_convq_act_trans(const Shard &sh, const ConvQWeights &w, int n_
 hipError_t launch_convq_rollout_trans(const Shard &sh, const ConvQWeights &w, int n_channels, int mode, double eps, uint64_t draw0,
                                       int32_t n_steps, uint32_t flags, int8_t *prev_boards, int fresh, int8_t *states_out,
                                       int8_t *prev_states_out, uint8_t *actions_out, uint32_t *recs_out, hipStream_t st);
-bool convq_trans_board_has_kernel(int height, int width);  // the board shapes the two launches above dispatch
+bool convq_trans_board_has_kernel(int height, int width);  // the board shapes the two launches above dispatch (CqTwoBoardShapes)
 // one member's hyper-parameters in device memory: the layouts of sgk_ppo_member_hyper / sgk_dqn_member_hyper (sgk.h; sgk_api.hip checks)
 struct PpoMemberHyper {
   double lr, clipping, critic_coeff, entropy_bonus;
