@@ -15,8 +15,9 @@ lr 0, the tables rewritten and invalidate_rows() between the phases): act + env.
 phase: the estimates cross launches, the quiet ones included), evaluate hbm behind a training phase, and one handle that alternates
 rollout phases with per-step phases; the time-limit plans through env.step, step_store and rollout hbm.
 
-Not covered: sgk_rollout_random*, sgk_policy_rollout* and sgk_convq_rollout* choose their own actions and cannot be scripted; the step
-server on WhiskyGold."""
+Not covered: the step server on WhiskyGold. sgk_rollout_random*, sgk_policy_rollout* and sgk_convq_rollout* choose their own actions
+and take no script: test_gpu_rollout_sweep.py plays these plans to a mid-plan step at which an env is drunk / has estimates that moved
+and holds the rollouts' launches from there to the oracle, without an event requirement of its own."""
 import contextlib
 import types
 

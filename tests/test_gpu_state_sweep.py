@@ -21,9 +21,10 @@ test_gpu_draw_sweeps.py (WhiskyGold and FriendFoe, the time limit and FriendFoe'
 env.step on BoatRace (step_store's STORE form and tabq_step_kernel among them); tabq act + env.step on a compact handle (it runs
 pitched; the fused tabular-Q calls run on both); the step server on levels other than BoatRace, IslandNavigation, AbsentSupervisor and ConveyorBelt.
 
-Out of scope: sgk_rollout_random(_stream), sgk_policy_rollout* and sgk_convq_rollout* choose their own actions and cannot be
-scripted; they share step_one with the paths above, and what the oracle's replay of their walks executes is listed in
-profiles/state_sweep/coverage.log."""
+Elsewhere: sgk_rollout_random(_stream), sgk_policy_rollout* and sgk_convq_rollout* choose their own actions and take no script.
+What each draws at the first step of a launch is known before the launch, so test_gpu_rollout_sweep.py deals every reachable state
+to envs that are going to draw the action it still needs, plants them through env.step and env.reset(mask) -- both swept here --
+and holds step 0 of the launch, which executes every pair, and a K-step continuation to the oracle (tests/rollout_sweep.py)."""
 import contextlib
 import types
 
