@@ -575,18 +575,28 @@ static inline int sgk_colour_of(int env_id, char ch, int rgb999[3]) {
   return 0;
 }
 
+/* THE list of levels, one entry each: X(public id of include/sgk.h, PREFIX here, ...). The prefix names SGK_ENV_<P>, SGK_<P>_H,
+ * SGK_<P>_W and SGK_<P>_ART above; what follows the macro's name is handed on to every entry. sgk_level_shape below, and in csrc/
+ * the kernels' geometry and the dispatch over levels (sgk_level_table.h) are generated from it, so a new level is its art and
+ * constants above, one line here, its rules (sgk_rules.cpp) and its transition (sgk_transition.h). This header does not include
+ * sgk.h: only a user that names the first column needs it. */
+#define SGK_LEVEL_LIST(X, ...)                        \
+  X(SGK_BOAT_RACE, BOAT, __VA_ARGS__)                 \
+  X(SGK_ISLAND_NAVIGATION, ISLAND, __VA_ARGS__)       \
+  X(SGK_SIDE_EFFECTS_SOKOBAN, SOKOBAN, __VA_ARGS__)   \
+  X(SGK_DISTRIBUTIONAL_SHIFT, LAVA, __VA_ARGS__)      \
+  X(SGK_WHISKY_GOLD, WHISKY, __VA_ARGS__)             \
+  X(SGK_ABSENT_SUPERVISOR, SUPER, __VA_ARGS__)        \
+  X(SGK_SAFE_INTERRUPTIBILITY, INTERRUPT, __VA_ARGS__) \
+  X(SGK_CONVEYOR_BELT, BELT, __VA_ARGS__)             \
+  X(SGK_TOMATO_WATERING, TOMATO, __VA_ARGS__)         \
+  X(SGK_FRIEND_FOE, FOE, __VA_ARGS__)
+
 static inline int sgk_level_shape(int env_id, int *H, int *W, const char *const **art) {
   switch (env_id) {
-  case SGK_ENV_BOAT: *H = SGK_BOAT_H; *W = SGK_BOAT_W; *art = SGK_BOAT_ART; return 0;
-  case SGK_ENV_ISLAND: *H = SGK_ISLAND_H; *W = SGK_ISLAND_W; *art = SGK_ISLAND_ART; return 0;
-  case SGK_ENV_SOKOBAN: *H = SGK_SOKOBAN_H; *W = SGK_SOKOBAN_W; *art = SGK_SOKOBAN_ART; return 0;
-  case SGK_ENV_LAVA: *H = SGK_LAVA_H; *W = SGK_LAVA_W; *art = SGK_LAVA_ART; return 0;
-  case SGK_ENV_WHISKY: *H = SGK_WHISKY_H; *W = SGK_WHISKY_W; *art = SGK_WHISKY_ART; return 0;
-  case SGK_ENV_SUPER: *H = SGK_SUPER_H; *W = SGK_SUPER_W; *art = SGK_SUPER_ART; return 0;
-  case SGK_ENV_INTERRUPT: *H = SGK_INTERRUPT_H; *W = SGK_INTERRUPT_W; *art = SGK_INTERRUPT_ART; return 0;
-  case SGK_ENV_BELT: *H = SGK_BELT_H; *W = SGK_BELT_W; *art = SGK_BELT_ART; return 0;
-  case SGK_ENV_TOMATO: *H = SGK_TOMATO_H; *W = SGK_TOMATO_W; *art = SGK_TOMATO_ART; return 0;
-  case SGK_ENV_FOE: *H = SGK_FOE_H; *W = SGK_FOE_W; *art = SGK_FOE_ART; return 0;
+#define SGK_LEVEL_SHAPE_CASE(ID, P, ...) case SGK_ENV_##P: *H = SGK_##P##_H; *W = SGK_##P##_W; *art = SGK_##P##_ART; return 0;
+    SGK_LEVEL_LIST(SGK_LEVEL_SHAPE_CASE, )
+#undef SGK_LEVEL_SHAPE_CASE
   default: return -1;
   }
 }

@@ -13,6 +13,7 @@
 
 #include "sgk_host_core.h"
 #include "sgk_kernels.h"
+#include "sgk_shapes.h"
 
 using sgk::host::fail;
 using sgk::host::GraphCache;
@@ -235,9 +236,8 @@ int sgk_create_ex(int env_id, int64_t n_envs, int device, uint64_t seed, uint64_
   s.env_base = env_index_base;
   s.n_cells = s.rules_host.n_cells;
   s.n_states = s.rules_host.n_states;
-  const int pitched = ((s.n_cells + 15) / 16) * 16;
   s.layout = layout;  // for 16-byte-multiple rows (IslandNavigation) both layouts have pitch == n_cells; they differ in who writes which bytes
-  s.pitch = (s.layout == SGK_LAYOUT_COMPACT) ? s.n_cells : pitched;
+  s.pitch = (s.layout == SGK_LAYOUT_COMPACT) ? s.n_cells : sgk::pitched_row_bytes(s.n_cells);
   const char *ng = getenv("SGK_NO_GRAPH");  // (the environment knobs of this file: the table in include/sgk.h)
   h->use_graph = !(ng && ng[0] == '1');
 
@@ -806,15 +806,23 @@ int sgk_epsilon_greedy(sgk_env *h, const float *scores_dev, double epsilon, uint
   return sgk_epsilon_greedy_ex(h, scores_dev, epsilon, draw_index, nullptr, nullptr, actions_out_dev);
 } SGK_CATCH_STATUS
 
+// what every MLP acting entry point refuses in its weights; `fn` is the name the width message carries
+static bool mlp_weights_null(const sgk_mlp_weights *w) { return !w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3; }
+static int mlp_weights_ok(const sgk_mlp_weights *w, const char *fn, const char *null_message = "NULL argument") {
+  if (mlp_weights_null(w)) return fail(SGK_ERR_INVALID, "%s", null_message);
+  if (!sgk::sizes_listed(sgk::MlpActWidths{}, w->n_hidden))
+    return fail(SGK_ERR_INVALID, "%s is built for n_hidden in {64, 100 (the reference default), 128}", fn);
+  return SGK_OK;
+}
+static sgk::PolicyWeights policy_weights(const sgk_mlp_weights *w) { return {w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden}; }
+
 int sgk_policy_act(sgk_env *h, const sgk_mlp_weights *w, double epsilon, uint64_t draw_index, const double *epsilon_dev,
                    const uint64_t *draw_index_dev, uint8_t *actions_out_dev, float *scores_out_dev) try {
   SGK_CHECK_HANDLE(h);
-  if (!w || !actions_out_dev || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3)
-    return fail(SGK_ERR_INVALID, "NULL argument");
-  if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
-    return fail(SGK_ERR_INVALID, "sgk_policy_act is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (!actions_out_dev) return fail(SGK_ERR_INVALID, "NULL argument");
+  if (int rc = mlp_weights_ok(w, "sgk_policy_act")) return rc;
   if (scores_out_dev && ((uintptr_t)scores_out_dev & 15u)) return fail(SGK_ERR_INVALID, "scores_out_dev must be 16-byte aligned");
-  sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
+  const sgk::PolicyWeights pw = policy_weights(w);
   SGK_HIP(sgk::launch_policy_act(h->sh, 0, pw, actions_out_dev, scores_out_dev, epsilon, draw_index, epsilon_dev, draw_index_dev,
                                  h->stream));
   return SGK_OK;
@@ -823,12 +831,10 @@ int sgk_policy_act(sgk_env *h, const sgk_mlp_weights *w, double epsilon, uint64_
 int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t draw_index, const uint64_t *draw_index_dev,
                       uint8_t *actions_out_dev, float *logits_out_dev) try {
   SGK_CHECK_HANDLE(h);
-  if (!w || !actions_out_dev || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3)
-    return fail(SGK_ERR_INVALID, "NULL argument");
-  if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
-    return fail(SGK_ERR_INVALID, "sgk_policy_sample is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (!actions_out_dev) return fail(SGK_ERR_INVALID, "NULL argument");
+  if (int rc = mlp_weights_ok(w, "sgk_policy_sample")) return rc;
   if (logits_out_dev && ((uintptr_t)logits_out_dev & 15u)) return fail(SGK_ERR_INVALID, "logits_out_dev must be 16-byte aligned");
-  sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
+  const sgk::PolicyWeights pw = policy_weights(w);
   SGK_HIP(sgk::launch_policy_act(h->sh, 1, pw, actions_out_dev, logits_out_dev, 0.0, draw_index, nullptr, draw_index_dev,
                                  h->stream));
   return SGK_OK;
@@ -837,10 +843,8 @@ int sgk_policy_sample(sgk_env *h, const sgk_mlp_weights *w, uint64_t draw_index,
 int sgk_policy_act_members_all(sgk_env *h, const sgk_mlp_weights *w, int32_t n_members, uint8_t *member_actions_out_dev,
                                float *member_scores_out_dev) try {
   // (the arguments first: the refusals need no handle and no device)
-  if (!w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3) return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: NULL weights");
-  if (!member_actions_out_dev) return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: member_actions_out_dev is NULL");
-  if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
-    return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (!mlp_weights_null(w) && !member_actions_out_dev) return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: member_actions_out_dev is NULL");
+  if (int rc = mlp_weights_ok(w, "sgk_policy_act_members_all", "sgk_policy_act_members_all: NULL weights")) return rc;
   if (n_members < 1 || n_members > SGK_MEMBERS_MAX)
     return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: n_members must be in 1..%d (got %d)", SGK_MEMBERS_MAX, (int)n_members);
   if (member_scores_out_dev && ((uintptr_t)member_scores_out_dev & 15u))
@@ -848,7 +852,7 @@ int sgk_policy_act_members_all(sgk_env *h, const sgk_mlp_weights *w, int32_t n_m
   SGK_CHECK_HANDLE(h);
   if (!sgk::mlp_cells_have_kernel(h->sh.n_cells))
     return fail(SGK_ERR_INVALID, "sgk_policy_act_members_all: the fused policy kernel does not cover boards of %d cells", h->sh.n_cells);
-  sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
+  const sgk::PolicyWeights pw = policy_weights(w);
   SGK_HIP(sgk::launch_policy_act_members(h->sh, pw, n_members, member_actions_out_dev, member_scores_out_dev, h->stream));
   return SGK_OK;
 } SGK_CATCH_STATUS
@@ -858,9 +862,7 @@ static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_m
                                int32_t n_steps, uint32_t flags, int8_t *states_out_dev, uint8_t *actions_out_dev,
                                sgk_step_rec *recs_out_dev, int64_t *member_metrics_dev, const double *member_epsilon_dev = nullptr) {
   SGK_CHECK_HANDLE(h);
-  if (!w || !w->w1t || !w->b1 || !w->w2 || !w->b2 || !w->w3t || !w->b3) return fail(SGK_ERR_INVALID, "NULL argument");
-  if (w->n_hidden != 64 && w->n_hidden != 100 && w->n_hidden != 128)
-    return fail(SGK_ERR_INVALID, "sgk_policy_rollout is built for n_hidden in {64, 100 (the reference default), 128}");
+  if (int rc = mlp_weights_ok(w, "sgk_policy_rollout")) return rc;
   if (n_members < 1) return fail(SGK_ERR_INVALID, "n_members must be >= 1 (got %d)", (int)n_members);
   if (h->sh.n % n_members != 0)
     return fail(SGK_ERR_INVALID, "n_envs (%lld) is not a multiple of n_members (%d): every member owns the same number of envs",
@@ -871,7 +873,7 @@ static int policy_rollout_impl(sgk_env *h, const sgk_mlp_weights *w, int32_t n_m
     return fail(SGK_ERR_INVALID, "only SGK_F_AUTO_RESET and SGK_F_MASK_FINISHED are meaningful here");
   if (n_steps == 0) return SGK_OK;
   sgk::Shard &s = h->sh;
-  sgk::PolicyWeights pw{w->w1t, w->b1, w->w2, w->b2, w->w3t, w->b3, w->n_hidden};
+  const sgk::PolicyWeights pw = policy_weights(w);
   SGK_HIP(sgk::launch_policy_rollout(s, mode, pw, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev,
                                      reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev,
                                      member_epsilon_dev));
@@ -922,10 +924,11 @@ static int convq_weights_ok(const sgk_convq_weights *w) {
   if (!w || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->wb || !w->bb || !w->wh || !w->bh || !w->wl || !w->bl)
     return fail(SGK_ERR_INVALID, "NULL argument");
   if (w->n_layers != 2) return fail(SGK_ERR_INVALID, "the fused conv body is built for n_layers == 2 (two 3 x 3 convolutions in the trunk)");
-  if (w->n_channels != 4 && w->n_channels != 5 && w->n_channels != 8)
+  if (!sgk::sizes_listed(sgk::CqChannels{}, w->n_channels))
     return fail(SGK_ERR_INVALID, "the fused conv body is built for n_channels in {4, 5 (policy_cnn.py's default), 8}");
   return SGK_OK;
 }
+static sgk::ConvQWeights convq_weights(const sgk_convq_weights *w) { return {w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl}; }
 
 static int convq_launch(sgk_env *h, const sgk_convq_weights *w, int mode, double epsilon, uint64_t draw_index, const double *epsilon_dev,
                         const uint64_t *draw_index_dev, uint8_t *actions_out_dev, float *scores_out_dev) {
@@ -933,7 +936,7 @@ static int convq_launch(sgk_env *h, const sgk_convq_weights *w, int mode, double
   if (int rc = convq_weights_ok(w)) return rc;
   if (!actions_out_dev) return fail(SGK_ERR_INVALID, "NULL argument");
   if (scores_out_dev && ((uintptr_t)scores_out_dev & 15u)) return fail(SGK_ERR_INVALID, "the scores / logits output must be 16-byte aligned");
-  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  const sgk::ConvQWeights cw = convq_weights(w);
   SGK_HIP(sgk::launch_convq_act(h->sh, cw, w->n_channels, mode, actions_out_dev, scores_out_dev, epsilon, draw_index, epsilon_dev,
                                 draw_index_dev, h->stream));
   return SGK_OK;
@@ -951,7 +954,7 @@ static int convq_rollout_impl(sgk_env *h, const sgk_convq_weights *w, int32_t n_
     return fail(SGK_ERR_INVALID, "only SGK_F_AUTO_RESET and SGK_F_MASK_FINISHED are meaningful here");
   if (n_steps == 0) return SGK_OK;
   sgk::Shard &s = h->sh;
-  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  const sgk::ConvQWeights cw = convq_weights(w);
   SGK_HIP(sgk::launch_convq_rollout(s, cw, w->n_channels, mode, epsilon, draw_index0, n_steps, flags, states_out_dev, actions_out_dev,
                                     reinterpret_cast<uint32_t *>(recs_out_dev), h->stream, n_members, member_metrics_dev));
   SGK_HIP(sgk::launch_reset(s, nullptr, 2, h->stream));  // materialise the boards of the final states
@@ -1006,7 +1009,7 @@ static int convq_trans_launch(sgk_env *h, const sgk_convq_weights *w, const sgk_
   if (!tr->actions_out_dev) return fail(SGK_ERR_INVALID, "%s: actions_out_dev is NULL", fn);
   if (tr->scores_out_dev && ((uintptr_t)tr->scores_out_dev & 15u))
     return fail(SGK_ERR_INVALID, "%s: the scores / logits output must be 16-byte aligned", fn);
-  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  const sgk::ConvQWeights cw = convq_weights(w);
   SGK_HIP(sgk::launch_convq_act_trans(h->sh, cw, w->n_channels, mode, tr->prev_boards_dev, tr->actions_out_dev, tr->scores_out_dev, epsilon,
                                       draw_index, epsilon_dev, draw_index_dev, h->stream));
   return SGK_OK;
@@ -1033,7 +1036,7 @@ int sgk_convq_rollout_trans(sgk_env *h, const sgk_convq_weights *w, const sgk_co
     return fail(SGK_ERR_INVALID, "only SGK_F_AUTO_RESET and SGK_F_MASK_FINISHED are meaningful here");
   if (n_steps == 0) return SGK_OK;
   sgk::Shard &s = h->sh;
-  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  const sgk::ConvQWeights cw = convq_weights(w);
   SGK_HIP(sgk::launch_convq_rollout_trans(s, cw, w->n_channels, mode, epsilon, draw_index0, n_steps, flags, tr->prev_boards_dev, tr->fresh,
                                           tr->states_out_dev, tr->prev_states_out_dev, tr->actions_out_dev,
                                           reinterpret_cast<uint32_t *>(tr->recs_out_dev), h->stream));
@@ -1057,7 +1060,7 @@ int sgk_convq_act_members_all(sgk_env *h, const sgk_convq_weights *w, int32_t n_
   if (!sgk::convq_board_has_kernel(h->sh.rules_host.height, h->sh.rules_host.width))
     return fail(SGK_ERR_INVALID, "sgk_convq_act_members_all: the fused conv body does not cover %d x %d boards", h->sh.rules_host.height,
                 h->sh.rules_host.width);
-  sgk::ConvQWeights cw{w->w1, w->b1, w->w2, w->b2, w->wb, w->bb, w->wh, w->bh, w->wl, w->bl};
+  const sgk::ConvQWeights cw = convq_weights(w);
   SGK_HIP(sgk::launch_convq_act_members(h->sh, cw, w->n_channels, n_members, out->member_actions_dev, out->member_scores_dev, h->stream));
   return SGK_OK;
 } SGK_CATCH_STATUS
@@ -1105,7 +1108,7 @@ static_assert(sizeof(sgk_dqn_member_hyper) == sizeof(sgk::DqnMemberHyper) && siz
               "the per-member hyper-parameter structs are plain doubles, the kernels' own layout");
 
 static bool dqn_shape_has_kernel(int n_cells, int n_hidden) {
-  return sgk::mlp_cells_have_kernel(n_cells) && (n_hidden == 64 || n_hidden == 100);
+  return sgk::mlp_cells_have_kernel(n_cells) && sgk::sizes_listed(sgk::MlpLearnWidths{}, n_hidden);
 }
 
 static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnResetStore *rs, const DqnMembers *mem = nullptr) {
@@ -1117,7 +1120,7 @@ static int dqn_sgd_step_impl(sgk_env *h, const sgk_dqn_learner *L, const DqnRese
     if (!p) return fail(SGK_ERR_INVALID, "NULL pointer in sgk_dqn_learner");
   for (int i = 0; i < 6; ++i)
     if (!L->m[i] || !L->v[i] || !L->vmax[i]) return fail(SGK_ERR_INVALID, "NULL Adam state in sgk_dqn_learner");
-  if ((L->n_hidden != 64 && L->n_hidden != 100) || L->batch < 1 || L->batch > 64 || L->slices_filled < 1)
+  if (!sgk::sizes_listed(sgk::MlpLearnWidths{}, L->n_hidden) || L->batch < 1 || L->batch > 64 || L->slices_filled < 1)
     return fail(SGK_ERR_INVALID, "sgk_dqn_sgd_step needs n_hidden 64 or 100 (the reference default), 1 <= batch <= 64, slices_filled >= 1");
   if (L->loss_mode != SGK_DQN_LOSS_REFERENCE && L->loss_mode != SGK_DQN_LOSS_PER_SAMPLE)
     return fail(SGK_ERR_INVALID, "loss_mode must be SGK_DQN_LOSS_REFERENCE (0) or SGK_DQN_LOSS_PER_SAMPLE (1)");
@@ -1236,7 +1239,7 @@ static int ppo_epochs_impl(sgk_env *h, const sgk_ppo_learner *L, int32_t n_membe
     if (!p) return fail(SGK_ERR_INVALID, "NULL pointer in sgk_ppo_learner");
   for (int i = 0; i < 8; ++i)
     if (!L->m[i] || !L->v[i]) return fail(SGK_ERR_INVALID, "NULL Adam state in sgk_ppo_learner");
-  if ((L->n_hidden != 64 && L->n_hidden != 100) || L->batch < 2 || L->batch > 64 || L->n_epochs < 1 || L->horizon < 1 ||
+  if (!sgk::sizes_listed(sgk::MlpLearnWidths{}, L->n_hidden) || L->batch < 2 || L->batch > 64 || L->n_epochs < 1 || L->horizon < 1 ||
       L->n_trajectories < 1 || L->n_trajectories >= (1ll << 31))
     return fail(SGK_ERR_INVALID, "sgk_ppo_epochs needs n_hidden 64 or 100 (the reference default), 2 <= batch <= 64, n_epochs >= 1, "
                                  "horizon >= 1, 1 <= n_trajectories < 2^31");

@@ -32,38 +32,7 @@ __device__ __forceinline__ void cq_static_for(F &&f) {
   }
 }
 
-// The board shapes and the channel counts the conv kernels are built for, each listed once. cq_dispatch calls f(board, channels) with
-// the compile-time values of the listed board that is height x width and of n_channels (f's `board` has ::H and ::W, `channels`
-// ::value) and returns what f returns; hipErrorInvalidValue where nothing is listed. The rollout, whose board follows from its level,
-// takes the channel half alone.
-template <int H_, int W_>
-struct CqBoard {
-  static constexpr int H = H_, W = W_;
-};
-template <class... B>
-struct CqBoards {};
-typedef CqBoards<CqBoard<5, 5>, CqBoard<6, 5>, CqBoard<6, 6>, CqBoard<6, 8>, CqBoard<7, 7>, CqBoard<7, 8>, CqBoard<7, 9>> CqOneBoardShapes;
-typedef CqBoards<CqBoard<5, 5>> CqTwoBoardShapes;  // BoatRace, the level TransitionBoatRace wraps; another level is one more entry
-
-template <class F>
-hipError_t cq_dispatch_channels(int n_channels, F &&f) {
-  switch (n_channels) {
-  case 5: return f(std::integral_constant<int, 5>{});
-  case 4: return f(std::integral_constant<int, 4>{});
-  case 8: return f(std::integral_constant<int, 8>{});
-  default: return hipErrorInvalidValue;
-  }
-}
-template <class... B, class F>
-hipError_t cq_dispatch(CqBoards<B...>, int height, int width, int n_channels, F &&f) {
-  hipError_t err = hipErrorInvalidValue;
-  (void)((B::H == height && B::W == width && (err = cq_dispatch_channels(n_channels, [&](auto channels) { return f(B{}, channels); }), true)) || ...);
-  return err;
-}
-template <class... B>
-bool cq_board_listed(CqBoards<B...>, int height, int width) {
-  return ((B::H == height && B::W == width) || ...);
-}
+// (the board shapes and channel counts these kernels are built for, and cq_dispatch over them: sgk_shapes.h)
 
 // CI: input planes. 1 = the board; 2 = the observation of a transition env, [previous board, board] (sgk_convq_*_trans): the inputs are
 // planes 0 .. CI - 1, and everything behind them sits CI - 1 planes higher.

@@ -15,19 +15,6 @@
 
 namespace sgk {
 
-template <int ENV>
-struct ConvDims;  // the level's board (sgk_levels.h); the conv kernels are specialised on (H, W)
-template <> struct ConvDims<SGK_BOAT_RACE> { static constexpr int H = 5, W = 5; };
-template <> struct ConvDims<SGK_ISLAND_NAVIGATION> { static constexpr int H = 6, W = 8; };
-template <> struct ConvDims<SGK_SIDE_EFFECTS_SOKOBAN> { static constexpr int H = 6, W = 6; };
-template <> struct ConvDims<SGK_DISTRIBUTIONAL_SHIFT> { static constexpr int H = 7, W = 9; };
-template <> struct ConvDims<SGK_WHISKY_GOLD> { static constexpr int H = 6, W = 8; };
-template <> struct ConvDims<SGK_ABSENT_SUPERVISOR> { static constexpr int H = 6, W = 8; };
-template <> struct ConvDims<SGK_SAFE_INTERRUPTIBILITY> { static constexpr int H = 7, W = 8; };
-template <> struct ConvDims<SGK_CONVEYOR_BELT> { static constexpr int H = 7, W = 7; };
-template <> struct ConvDims<SGK_TOMATO_WATERING> { static constexpr int H = 7, W = 9; };
-template <> struct ConvDims<SGK_FRIEND_FOE> { static constexpr int H = 6, W = 5; };
-
 struct ConvRolloutArgs {
   StepArgs env;          // state / rec / episode arrays / metrics / rules / n / seed / env_base / flags
   double eps;            // mode 0
@@ -64,7 +51,7 @@ using ConvRolloutArgsFor =
 // (CI = 1: no previous rows and two arrays of flags -- the offsets from before the two-board observation)
 template <int ENV, int C, int CI = 1>
 struct ConvRolloutLds {
-  typedef ConvQGeom<ConvDims<ENV>::H, ConvDims<ENV>::W, C, CI> G;
+  typedef ConvQGeom<Geom<ENV>::H, Geom<ENV>::W, C, CI> G;
   static constexpr size_t tile_bytes = (size_t)G::ENVS * G::NC;
   static constexpr size_t o_tile = (G::lds_bytes + 15) & ~(size_t)15;                      // int8 [ENVS][NC]: the current rows
   static constexpr size_t o_prev = (o_tile + tile_bytes + 15) & ~(size_t)15;               // CI = 2: int8 [ENVS][NC], the previous rows
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(CQ_WG, CQ_ROLLOUT_WAVES_FOR(C)) void convq_rollout_
     const float *__restrict__ b2r, const float *__restrict__ wbr, const float *__restrict__ bbr, const float *__restrict__ whr,
     const float *__restrict__ bhr, const float *__restrict__ wlr, const float *__restrict__ blr) {
   static_assert(!(MEMBERS && CI == 2), "the two-board kernel has no member form");
-  constexpr int WW = ConvDims<ENV>::W;
+  constexpr int WW = Geom<ENV>::W;
   typedef ConvRolloutLds<ENV, C, CI> LD;
   typedef typename LD::G G;
   static_assert(G::NC == Geom<ENV>::NC, "level geometry");
@@ -282,7 +269,7 @@ static hipError_t convq_rollout_launch(const Shard &sh, const ConvQWeights &w, C
   typedef ConvRolloutLds<E, CV, CI> LD;
   constexpr size_t lds = LD::bytes;
   static_assert(lds <= 160u * 1024u, "convq rollout LDS plan");
-  if (ConvDims<E>::H != sh.rules_host.height || ConvDims<E>::W != sh.rules_host.width) return hipErrorInvalidValue;
+  if (Geom<E>::H != sh.rules_host.height || Geom<E>::W != sh.rules_host.width) return hipErrorInvalidValue;
   hipError_t ae = allow_dynamic_lds<convq_rollout_kernel<E, CV, MEMBERS, CI>>(sh.device, (int)lds);
   if (ae != hipSuccess) return ae;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(CQ_ROLLOUT_WAVES_FOR(CV), (160u * 1024u) / lds));

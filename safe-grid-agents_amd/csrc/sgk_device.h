@@ -21,7 +21,8 @@
 #include <atomic>
 
 #include "sgk_kernels.h"
-#include "sgk_transition.h"  // EnvState, the counter RNG, transition<ENV>, begin_episode<ENV>, env_actual_action<ENV>
+#include "sgk_shapes.h"      // the shapes with a kernel: SGK_DISPATCH_CELLS, the conv and hidden-width lists
+#include "sgk_transition.h"  // Geom<ENV>, SGK_DISPATCH_ENV[_LAYOUT], EnvState, the counter RNG, transition<ENV>, begin_episode<ENV>, env_actual_action<ENV>
 
 
 namespace sgk {
@@ -537,29 +538,6 @@ __device__ __noinline__ void write_row_bytes(const SgkRules &R, int8_t *__restri
   }
 }
 
-template <int ENV>
-struct Geom;
-template <>
-struct Geom<SGK_BOAT_RACE> { static constexpr int NC = 25, PITCH = 32; };
-template <>
-struct Geom<SGK_ISLAND_NAVIGATION> { static constexpr int NC = 48, PITCH = 48; };
-template <>
-struct Geom<SGK_SIDE_EFFECTS_SOKOBAN> { static constexpr int NC = 36, PITCH = 48; };
-template <>
-struct Geom<SGK_DISTRIBUTIONAL_SHIFT> { static constexpr int NC = 63, PITCH = 64; };
-template <>
-struct Geom<SGK_WHISKY_GOLD> { static constexpr int NC = 48, PITCH = 48; };
-template <>
-struct Geom<SGK_ABSENT_SUPERVISOR> { static constexpr int NC = 48, PITCH = 48; };
-template <>
-struct Geom<SGK_SAFE_INTERRUPTIBILITY> { static constexpr int NC = 56, PITCH = 64; };
-template <>
-struct Geom<SGK_CONVEYOR_BELT> { static constexpr int NC = 49, PITCH = 64; };
-template <>
-struct Geom<SGK_TOMATO_WATERING> { static constexpr int NC = 63, PITCH = 64; };
-template <>
-struct Geom<SGK_FRIEND_FOE> { static constexpr int NC = 30, PITCH = 32; };
-
 // numpy's 53-bit uniform from two 32-bit draws (random_sample)
 __device__ __forceinline__ double uniform53(uint32_t a, uint32_t b) {
   return (double)((((uint64_t)(a >> 5)) << 26) + (uint64_t)(b >> 6)) / 9007199254740992.0;
@@ -644,69 +622,6 @@ static hipError_t allow_dynamic_lds(int device, int bytes) {
   if (e == hipSuccess) opted_in.fetch_or(1ull << (device & 63));
   return e;
 }
-
-#define SGK_DISPATCH_ENV_LAYOUT(ENVID, LAYOUT, ...)                                                     \
-  do {                                                                                                     \
-    if ((LAYOUT) == SGK_LAYOUT_COMPACT) {                                                                  \
-      switch (ENVID) {                                                                                     \
-      case SGK_BOAT_RACE: { constexpr int E = SGK_BOAT_RACE; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break;         \
-      case SGK_ISLAND_NAVIGATION: { constexpr int E = SGK_ISLAND_NAVIGATION; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_DISTRIBUTIONAL_SHIFT: { constexpr int E = SGK_DISTRIBUTIONAL_SHIFT; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_WHISKY_GOLD: { constexpr int E = SGK_WHISKY_GOLD; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_ABSENT_SUPERVISOR: { constexpr int E = SGK_ABSENT_SUPERVISOR; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_SAFE_INTERRUPTIBILITY: { constexpr int E = SGK_SAFE_INTERRUPTIBILITY; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_CONVEYOR_BELT: { constexpr int E = SGK_CONVEYOR_BELT; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_TOMATO_WATERING: { constexpr int E = SGK_TOMATO_WATERING; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      case SGK_FRIEND_FOE: { constexpr int E = SGK_FRIEND_FOE; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break; \
-      default: { constexpr int E = SGK_SIDE_EFFECTS_SOKOBAN; constexpr int L = SGK_LAYOUT_COMPACT; __VA_ARGS__; } break;         \
-      }                                                                                                    \
-    } else {                                                                                               \
-      switch (ENVID) {                                                                                     \
-      case SGK_BOAT_RACE: { constexpr int E = SGK_BOAT_RACE; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break;         \
-      case SGK_ISLAND_NAVIGATION: { constexpr int E = SGK_ISLAND_NAVIGATION; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_DISTRIBUTIONAL_SHIFT: { constexpr int E = SGK_DISTRIBUTIONAL_SHIFT; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_WHISKY_GOLD: { constexpr int E = SGK_WHISKY_GOLD; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_ABSENT_SUPERVISOR: { constexpr int E = SGK_ABSENT_SUPERVISOR; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_SAFE_INTERRUPTIBILITY: { constexpr int E = SGK_SAFE_INTERRUPTIBILITY; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_CONVEYOR_BELT: { constexpr int E = SGK_CONVEYOR_BELT; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_TOMATO_WATERING: { constexpr int E = SGK_TOMATO_WATERING; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      case SGK_FRIEND_FOE: { constexpr int E = SGK_FRIEND_FOE; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break; \
-      default: { constexpr int E = SGK_SIDE_EFFECTS_SOKOBAN; constexpr int L = SGK_LAYOUT_PITCHED; __VA_ARGS__; } break;         \
-      }                                                                                                    \
-    }                                                                                                      \
-  } while (0)
-
-#define SGK_DISPATCH_ENV(ENVID, ...)                                                  \
-  do {                                                                                   \
-    switch (ENVID) {                                                                     \
-    case SGK_BOAT_RACE: { constexpr int E = SGK_BOAT_RACE; __VA_ARGS__; } break;               \
-    case SGK_ISLAND_NAVIGATION: { constexpr int E = SGK_ISLAND_NAVIGATION; __VA_ARGS__; } break; \
-    case SGK_DISTRIBUTIONAL_SHIFT: { constexpr int E = SGK_DISTRIBUTIONAL_SHIFT; __VA_ARGS__; } break; \
-    case SGK_WHISKY_GOLD: { constexpr int E = SGK_WHISKY_GOLD; __VA_ARGS__; } break; \
-    case SGK_ABSENT_SUPERVISOR: { constexpr int E = SGK_ABSENT_SUPERVISOR; __VA_ARGS__; } break; \
-    case SGK_SAFE_INTERRUPTIBILITY: { constexpr int E = SGK_SAFE_INTERRUPTIBILITY; __VA_ARGS__; } break; \
-    case SGK_CONVEYOR_BELT: { constexpr int E = SGK_CONVEYOR_BELT; __VA_ARGS__; } break; \
-    case SGK_TOMATO_WATERING: { constexpr int E = SGK_TOMATO_WATERING; __VA_ARGS__; } break; \
-    case SGK_FRIEND_FOE: { constexpr int E = SGK_FRIEND_FOE; __VA_ARGS__; } break; \
-    default: { constexpr int E = SGK_SIDE_EFFECTS_SOKOBAN; __VA_ARGS__; } break;               \
-    }                                                                                    \
-  } while (0)
-
-// The board sizes (cells) the MLP kernels are instantiated for -- policy forward, DQN and PPO learners; mlp_cells_have_kernel() is
-// this list. Binds K0; a size without a kernel returns hipErrorInvalidValue from the calling function.
-#define SGK_DISPATCH_CELLS(NCELLS, ...)                                \
-  do {                                                                 \
-    switch (NCELLS) {                                                  \
-    case 25: { constexpr int K0 = 25; __VA_ARGS__; } break;            \
-    case 30: { constexpr int K0 = 30; __VA_ARGS__; } break;            \
-    case 36: { constexpr int K0 = 36; __VA_ARGS__; } break;            \
-    case 48: { constexpr int K0 = 48; __VA_ARGS__; } break;            \
-    case 49: { constexpr int K0 = 49; __VA_ARGS__; } break;            \
-    case 56: { constexpr int K0 = 56; __VA_ARGS__; } break;            \
-    case 63: { constexpr int K0 = 63; __VA_ARGS__; } break;            \
-    default: return hipErrorInvalidValue;                              \
-    }                                                                  \
-  } while (0)
 
 static inline StepArgs make_step_args(const Shard &sh, const uint8_t *actions, uint32_t flags) {
   StepArgs a;

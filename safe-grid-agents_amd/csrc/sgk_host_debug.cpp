@@ -15,24 +15,12 @@ int host_debug_transition(const SgkRules &R, int agent_cell, int box_cell, int a
   s.pos = agent_cell; s.box = box_cell & 0xff; s.frame = 0; s.over = 0; s.ret = 0; s.hid = 0; s.epi = 0; s.ext = 0; s.draws = 0;
   s.mode = (box_cell >> 8) & 1;  // the debug hook carries the state word's mode bit above the box byte
   int r_obs = 0, r_hid = 0, term = 0;
-  switch (R.env_id) {
-  case SGK_BOAT_RACE: transition<SGK_BOAT_RACE>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_ISLAND_NAVIGATION: transition<SGK_ISLAND_NAVIGATION>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_SIDE_EFFECTS_SOKOBAN: transition<SGK_SIDE_EFFECTS_SOKOBAN>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_DISTRIBUTIONAL_SHIFT: transition<SGK_DISTRIBUTIONAL_SHIFT>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_WHISKY_GOLD: transition<SGK_WHISKY_GOLD>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_ABSENT_SUPERVISOR: transition<SGK_ABSENT_SUPERVISOR>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_CONVEYOR_BELT: transition<SGK_CONVEYOR_BELT>(R, s, action, r_obs, r_hid, term); break;
-  case SGK_TOMATO_WATERING: transition<SGK_TOMATO_WATERING>(R, s, action, r_obs, r_hid, term); break;  // (no drying: s.draws = 0)
-  case SGK_FRIEND_FOE: transition<SGK_FRIEND_FOE>(R, s, action, r_obs, r_hid, term); break;  // (level 0, no estimator update)
-  case SGK_SAFE_INTERRUPTIBILITY: {
+  if (!level_listed(R.env_id)) return -1;
+  SGK_DISPATCH_ENV(R.env_id, {
     // the hook is handed the action the AGENT chose: the interruption drape's substitution is part of the kernels' step
-    const int executed = env_actual_action<SGK_SAFE_INTERRUPTIBILITY>(R, s, 0, 0, action);
-    transition<SGK_SAFE_INTERRUPTIBILITY>(R, s, executed, r_obs, r_hid, term);
-    break;
-  }
-  default: return -1;
-  }
+    if constexpr (E == SGK_SAFE_INTERRUPTIBILITY) action = env_actual_action<E>(R, s, 0, 0, action);
+    transition<E>(R, s, action, r_obs, r_hid, term);  // (tomato watering: no drying, s.draws = 0; friend or foe: level 0, no estimator update)
+  });
   out[0] = s.pos; out[1] = s.box; out[2] = r_obs; out[3] = r_hid; out[4] = term | (s.mode << 1);  // bit 1: the mode bit after the step
   return 0;
 }
@@ -58,19 +46,8 @@ int host_debug_step(const SgkRules &R, uint64_t word, int n_resets, int action, 
                     int out[4], double *aux) {
   EnvState s = unpack_state(word);
   s.epi = n_resets;
-  switch (R.env_id) {
-  case SGK_BOAT_RACE: host_step_env<SGK_BOAT_RACE>(R, s, action, seed, env, out, aux); break;
-  case SGK_ISLAND_NAVIGATION: host_step_env<SGK_ISLAND_NAVIGATION>(R, s, action, seed, env, out, aux); break;
-  case SGK_SIDE_EFFECTS_SOKOBAN: host_step_env<SGK_SIDE_EFFECTS_SOKOBAN>(R, s, action, seed, env, out, aux); break;
-  case SGK_DISTRIBUTIONAL_SHIFT: host_step_env<SGK_DISTRIBUTIONAL_SHIFT>(R, s, action, seed, env, out, aux); break;
-  case SGK_WHISKY_GOLD: host_step_env<SGK_WHISKY_GOLD>(R, s, action, seed, env, out, aux); break;
-  case SGK_ABSENT_SUPERVISOR: host_step_env<SGK_ABSENT_SUPERVISOR>(R, s, action, seed, env, out, aux); break;
-  case SGK_SAFE_INTERRUPTIBILITY: host_step_env<SGK_SAFE_INTERRUPTIBILITY>(R, s, action, seed, env, out, aux); break;
-  case SGK_CONVEYOR_BELT: host_step_env<SGK_CONVEYOR_BELT>(R, s, action, seed, env, out, aux); break;
-  case SGK_TOMATO_WATERING: host_step_env<SGK_TOMATO_WATERING>(R, s, action, seed, env, out, aux); break;
-  case SGK_FRIEND_FOE: host_step_env<SGK_FRIEND_FOE>(R, s, action, seed, env, out, aux); break;
-  default: return -1;
-  }
+  if (!level_listed(R.env_id)) return -1;
+  SGK_DISPATCH_ENV(R.env_id, host_step_env<E>(R, s, action, seed, env, out, aux));
   *word_out = pack_state(s);
   return 0;
 }
@@ -79,12 +56,8 @@ int host_debug_step(const SgkRules &R, uint64_t word, int n_resets, int action, 
 uint64_t host_reset_word(const SgkRules &R, uint64_t seed, uint64_t env, int n_resets, const double *aux) {
   EnvState s = initial_state(R);
   s.epi = n_resets;
-  switch (R.env_id) {
-  case SGK_ABSENT_SUPERVISOR: begin_episode<SGK_ABSENT_SUPERVISOR>(R, s, seed, env); break;
-  case SGK_SAFE_INTERRUPTIBILITY: begin_episode<SGK_SAFE_INTERRUPTIBILITY>(R, s, seed, env); break;
-  case SGK_FRIEND_FOE: begin_episode<SGK_FRIEND_FOE>(R, s, seed, env, aux); break;
-  default: break;
-  }
+  // (begin_episode decides something for three levels -- absent supervisor, safe interruptibility, friend or foe -- and nothing elsewhere)
+  SGK_DISPATCH_ENV(R.env_id, begin_episode<E>(R, s, seed, env, aux));
   return pack_state(s);
 }
 
@@ -98,11 +71,8 @@ int host_random_action(uint64_t seed, uint64_t env, uint64_t t) {
 int host_episode_coin(const SgkRules &R, uint64_t seed, uint64_t env, int n_resets) {
   EnvState s = initial_state(R);
   s.epi = n_resets;
-  switch (R.env_id) {
-  case SGK_ABSENT_SUPERVISOR: begin_episode<SGK_ABSENT_SUPERVISOR>(R, s, seed, env); break;
-  case SGK_SAFE_INTERRUPTIBILITY: begin_episode<SGK_SAFE_INTERRUPTIBILITY>(R, s, seed, env); break;
-  default: return -1;
-  }
+  if (R.env_id != SGK_ABSENT_SUPERVISOR && R.env_id != SGK_SAFE_INTERRUPTIBILITY) return -1;  // the levels with a coin
+  SGK_DISPATCH_ENV(R.env_id, begin_episode<E>(R, s, seed, env));
   return s.mode;
 }
 

@@ -114,7 +114,7 @@ hipError_t launch_convq_act(const Shard &sh, const ConvQWeights &w, int n_channe
 // member_scores [n_members][n][4] or null
 hipError_t launch_convq_act_members(const Shard &sh, const ConvQWeights &w, int n_channels, int n_members, uint8_t *member_actions,
                                     float *member_scores, hipStream_t st);
-bool convq_board_has_kernel(int height, int width);  // the board shapes launch_convq_act dispatches (sgk_convq.h's CqOneBoardShapes)
+bool convq_board_has_kernel(int height, int width);  // the board shapes launch_convq_act dispatches (sgk_shapes.h's CqOneBoardShapes)
 // n_steps of {conv forward, draw, env.step} in one launch (sgk_convq_rollout.hip); outputs as for launch_policy_rollout.
 // n_members >= 1 (sgk_convq_rollout_members; 0: sgk_convq_rollout's own kernel): `w` addresses member 0 of the ten weight tensors stacked
 // [n_members][...], member m acts in the envs m * n / n_members ..; member_metrics as for launch_policy_rollout
@@ -181,7 +181,7 @@ hipError_t launch_reset_done_store(const Shard &sh, uint32_t flags, int64_t slic
 hipError_t launch_replay_store(const Shard &sh, int phase, const uint8_t *actions, int cheat, int64_t head, const long long *head_dev,
                                int8_t *states, int8_t *successors, uint8_t *r_actions, int8_t *r_rewards, uint8_t *r_terminals,
                                hipStream_t st);
-bool mlp_cells_have_kernel(int n_cells);  // the board sizes SGK_DISPATCH_CELLS (sgk_device.h) lists: MLP forward, DQN and PPO learners
+bool mlp_cells_have_kernel(int n_cells);  // the board sizes SGK_DISPATCH_CELLS (sgk_shapes.h) lists: MLP forward, DQN and PPO learners
 size_t dqn_sgd_lds_bytes(int n_cells, int n_hidden);
 size_t dqn_sgd_scratch_bytes(int n_cells, int n_hidden);
 size_t dqn_members_scratch_stride(int n_cells, int n_hidden);

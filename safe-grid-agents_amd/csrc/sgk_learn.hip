@@ -1350,10 +1350,7 @@ size_t dqn_members_scratch_stride(int n_cells, int n_hidden) {
   return (sizeof(AdamHeader) + sizeof(float) * dqn_param_count(n_cells, n_hidden) + 15) & ~(size_t)15;
 }
 
-bool mlp_cells_have_kernel(int n_cells) {
-  const auto dispatch = [](int n) -> hipError_t { SGK_DISPATCH_CELLS(n, { (void)K0; return hipSuccess; }); };
-  return dispatch(n_cells) == hipSuccess;
-}
+bool mlp_cells_have_kernel(int n_cells) { return mlp_cells_listed(n_cells); }
 
 // the SGD kernel of one shape (the 160 KB dynamic-LDS opt-in is made on its first launch per device)
 template <int K0, int H, bool MEMBERS, bool HYPER = false>
@@ -1412,9 +1409,10 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
   a.max_norm = (float)L.max_grad_norm;
   const bool adam = a.adam_scratch && !L.reset_store;
   hipError_t se = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
-  SGK_DISPATCH_CELLS(sh.n_cells, {  // the shapes with an instantiation: the levels' board sizes x {64, 100} hidden units
-    if (L.n_hidden == 100) se = launch_sgd_adam<K0, 100>(a, n_members, adam, lds, sh.device, st);
-    else if (L.n_hidden == 64) se = launch_sgd_adam<K0, 64>(a, n_members, adam, lds, sh.device, st);
+  SGK_DISPATCH_CELLS(sh.n_cells, {  // the shapes with an instantiation: the levels' board sizes x the learners' hidden widths
+    se = sizes_dispatch(MlpLearnWidths{}, L.n_hidden, [&](auto width) {
+      return launch_sgd_adam<K0, decltype(width)::value>(a, n_members, adam, lds, sh.device, st);
+    });
   });
   if (se != hipSuccess) return se;
   if (L.reset_store) {  // Adam + reset_done + the next transitions' states in ONE launch behind the SGD kernel
@@ -1427,18 +1425,15 @@ hipError_t launch_dqn_sgd(const Shard &sh, const DqnLearner &L, hipStream_t st) 
     r.mode_flags = 1 | ((L.rs_flags & SGK_F_NO_BOARDS) ? 4 : 0);
     r.st = make_store(sh, L.rs_states_ring, nullptr, nullptr, nullptr, L.rs_slice, L.rs_slice_dev, L.rs_ring, 0);
     const int reset_blocks = grid_for((sh.n + WG - 1) / WG, sh.max_grid);
-#define SGK_ADAM_RESET(HV)                                                                                                 \
-  do {                                                                                                                     \
-    const int adam_blocks = (ParamMap<Geom<E>::NC, HV>::P + 255) / 256;                                                    \
-    dqn_adam_reset_kernel<HV, E, L><<<dim3(adam_blocks + reset_blocks), dim3(256), 0, st>>>(a, adam_blocks, r);            \
-  } while (0)
-    const int nh = a.n_hidden;
     SGK_DISPATCH_ENV_LAYOUT(sh.env_id, sh.layout, {
       if (Geom<E>::NC != sh.n_cells) return hipErrorInvalidValue;
-      if (nh == 100) SGK_ADAM_RESET(100);
-      else SGK_ADAM_RESET(64);
+      (void)sizes_dispatch(MlpLearnWidths{}, a.n_hidden, [&](auto width) {  // (a listed width: the SGD launch above took it)
+        constexpr int HV = decltype(width)::value;
+        const int adam_blocks = (ParamMap<Geom<E>::NC, HV>::P + 255) / 256;
+        dqn_adam_reset_kernel<HV, E, L><<<dim3(adam_blocks + reset_blocks), dim3(256), 0, st>>>(a, adam_blocks, r);
+        return hipSuccess;
+      });
     });
-#undef SGK_ADAM_RESET
   }
   return hipGetLastError();
 }
@@ -1489,8 +1484,9 @@ hipError_t launch_ppo_epochs(const Shard &sh, const PpoLearner &P, hipStream_t s
   a.clipping = (float)P.clipping; a.critic_coeff = (float)P.critic_coeff; a.entropy_bonus = (float)P.entropy_bonus;
   hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
   SGK_DISPATCH_CELLS(sh.n_cells, {
-    if (P.n_hidden == 100) le = launch_ppo<K0, 100>(a, n_members, lds, sh.device, st);
-    else if (P.n_hidden == 64) le = launch_ppo<K0, 64>(a, n_members, lds, sh.device, st);
+    le = sizes_dispatch(MlpLearnWidths{}, P.n_hidden, [&](auto width) {
+      return launch_ppo<K0, decltype(width)::value>(a, n_members, lds, sh.device, st);
+    });
   });
   if (le != hipSuccess) return le;
   return hipGetLastError();

@@ -573,17 +573,13 @@ hipError_t launch_policy_act(const Shard &sh, int mode, const PolicyWeights &w, 
                              uint64_t draw, const double *eps_dev, const uint64_t *draw_dev, hipStream_t st) {
   (void)hipGetLastError();
   hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
-#define SGK_POLICY_LAUNCH(HID)                                                                              \
-  (mode == 0 ? launch_act<K0, HID, 0>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st)              \
-             : launch_act<K0, HID, 1>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st))
   SGK_DISPATCH_CELLS(sh.n_cells, {
-    switch (w.n_hidden) {  // hidden widths with an instantiation: the reference default (100) and the two common powers of two
-    case 64: le = SGK_POLICY_LAUNCH(64); break;
-    case 100: le = SGK_POLICY_LAUNCH(100); break;
-    case 128: le = SGK_POLICY_LAUNCH(128); break;
-    }
+    le = sizes_dispatch(MlpActWidths{}, w.n_hidden, [&](auto width) {
+      constexpr int HID = decltype(width)::value;
+      return mode == 0 ? launch_act<K0, HID, 0>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st)
+                       : launch_act<K0, HID, 1>(sh, w, actions, scores, eps, draw, eps_dev, draw_dev, st);
+    });
   });
-#undef SGK_POLICY_LAUNCH
   if (le != hipSuccess) return le;
   return hipGetLastError();
 }
@@ -612,11 +608,9 @@ hipError_t launch_policy_act_members(const Shard &sh, const PolicyWeights &w, in
   if (n_members < 1 || n_members > SGK_MEMBERS_MAX) return hipErrorInvalidValue;
   hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
   SGK_DISPATCH_CELLS(sh.n_cells, {
-    switch (w.n_hidden) {
-    case 64: le = launch_act_members<K0, 64>(sh, w, n_members, member_actions, member_scores, st); break;
-    case 100: le = launch_act_members<K0, 100>(sh, w, n_members, member_actions, member_scores, st); break;
-    case 128: le = launch_act_members<K0, 128>(sh, w, n_members, member_actions, member_scores, st); break;
-    }
+    le = sizes_dispatch(MlpActWidths{}, w.n_hidden, [&](auto width) {
+      return launch_act_members<K0, decltype(width)::value>(sh, w, n_members, member_actions, member_scores, st);
+    });
   });
   if (le != hipSuccess) return le;
   return hipGetLastError();
@@ -653,17 +647,13 @@ hipError_t launch_policy_rollout(const Shard &sh, int mode, const PolicyWeights 
   a.member_eps = member_eps;
   const int grid = n_members * a.member_wgs;
   hipError_t le = hipErrorInvalidValue;  // (what a hidden width without an instantiation leaves)
-#define SGK_ROLLOUT_LAUNCH(HID)                                                                                \
-  (member_eps ? launch_rollout<E, HID, 0, true>(a, grid, sh.device, st)                                        \
-              : mode == 0 ? launch_rollout<E, HID, 0>(a, grid, sh.device, st) : launch_rollout<E, HID, 1>(a, grid, sh.device, st))
   SGK_DISPATCH_ENV(sh.env_id, {
-    switch (w.n_hidden) {
-    case 64: le = SGK_ROLLOUT_LAUNCH(64); break;
-    case 100: le = SGK_ROLLOUT_LAUNCH(100); break;
-    case 128: le = SGK_ROLLOUT_LAUNCH(128); break;
-    }
+    le = sizes_dispatch(MlpActWidths{}, w.n_hidden, [&](auto width) {
+      constexpr int HID = decltype(width)::value;
+      return member_eps ? launch_rollout<E, HID, 0, true>(a, grid, sh.device, st)
+                        : mode == 0 ? launch_rollout<E, HID, 0>(a, grid, sh.device, st) : launch_rollout<E, HID, 1>(a, grid, sh.device, st);
+    });
   });
-#undef SGK_ROLLOUT_LAUNCH
   if (le != hipSuccess) return le;
   return hipGetLastError();
 }

@@ -547,10 +547,9 @@ __global__ __launch_bounds__(PC_WG) void ppo_cnn_adam_kernel(typename PcArgs<CIN
   if (e == 0) a.step[mem] = step + 1;
 }
 
+// the shapes of the acting kernels, through their lists (sgk_shapes.h)
 bool ppo_cnn_shape_supported(int height, int width, int n_channels) {
-  const bool shape = (height == 5 && width == 5) || (height == 6 && width == 5) || (height == 6 && width == 6) || (height == 6 && width == 8) ||
-                     (height == 7 && width == 7) || (height == 7 && width == 8) || (height == 7 && width == 9);
-  return shape && (n_channels == 4 || n_channels == 5 || n_channels == 8);
+  return cq_board_listed(CqOneBoardShapes{}, height, width) && sizes_listed(CqChannels{}, n_channels);
 }
 
 template <int HH, int WW, int C, bool MEMBERS, bool HYPER = false, int CIN = 1>
@@ -607,34 +606,16 @@ hipError_t launch_ppo_cnn_epochs(const Shard &sh, const PpoCnnLearner &P, hipStr
   a.ws_stride = ppo_cnn_members_stride_bytes(H, W, C, P.batch) / sizeof(float);
   a.n_epochs = P.n_epochs;
   a.member_hyper = member_hyper;
-#define SGK_PC_LAUNCH_C(HV, WV)                                                                                            \
-  do {                                                                                                                     \
-    if (member_hyper) {                                                                                                    \
-      if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, true, true>(a, P.n_epochs, n_members, st);                        \
-      if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, true, true>(a, P.n_epochs, n_members, st);                        \
-      return launch_ppo_cnn_shape<HV, WV, 8, true, true>(a, P.n_epochs, n_members, st);                                    \
-    }                                                                                                                      \
-    if (n_members > 0) {                                                                                                   \
-      if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, true>(a, P.n_epochs, n_members, st);                              \
-      if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, true>(a, P.n_epochs, n_members, st);                              \
-      return launch_ppo_cnn_shape<HV, WV, 8, true>(a, P.n_epochs, n_members, st);                                          \
-    }                                                                                                                      \
-    if (C == 5) return launch_ppo_cnn_shape<HV, WV, 5, false>(a, P.n_epochs, 1, st);                                       \
-    if (C == 4) return launch_ppo_cnn_shape<HV, WV, 4, false>(a, P.n_epochs, 1, st);                                       \
-    return launch_ppo_cnn_shape<HV, WV, 8, false>(a, P.n_epochs, 1, st);                                                   \
-  } while (0)
-  if (H == 5 && W == 5) SGK_PC_LAUNCH_C(5, 5);
-  if (H == 6 && W == 5) SGK_PC_LAUNCH_C(6, 5);
-  if (H == 6 && W == 6) SGK_PC_LAUNCH_C(6, 6);
-  if (H == 6 && W == 8) SGK_PC_LAUNCH_C(6, 8);
-  if (H == 7 && W == 7) SGK_PC_LAUNCH_C(7, 7);
-  if (H == 7 && W == 8) SGK_PC_LAUNCH_C(7, 8);
-  SGK_PC_LAUNCH_C(7, 9);
-#undef SGK_PC_LAUNCH_C
+  return cq_dispatch(CqOneBoardShapes{}, H, W, C, [&](auto board, auto channels) {
+    constexpr int HV = decltype(board)::H, WV = decltype(board)::W, CV = decltype(channels)::value;
+    if (member_hyper) return launch_ppo_cnn_shape<HV, WV, CV, true, true>(a, P.n_epochs, n_members, st);
+    if (n_members > 0) return launch_ppo_cnn_shape<HV, WV, CV, true>(a, P.n_epochs, n_members, st);
+    return launch_ppo_cnn_shape<HV, WV, CV, false>(a, P.n_epochs, 1, st);
+  });
 }
 
-bool ppo_cnn_trans_shape_supported(int height, int width, int n_channels) {
-  return height == 5 && width == 5 && (n_channels == 4 || n_channels == 5 || n_channels == 8);  // the shapes sgk_convq_*_trans act on
+bool ppo_cnn_trans_shape_supported(int height, int width, int n_channels) {  // the shapes sgk_convq_*_trans act on
+  return cq_board_listed(CqTwoBoardShapes{}, height, width) && sizes_listed(CqChannels{}, n_channels);
 }
 
 hipError_t launch_ppo_cnn_epochs_trans(const Shard &sh, const PpoCnnLearner &P, const int8_t *prev_states, hipStream_t st) {
@@ -645,9 +626,9 @@ hipError_t launch_ppo_cnn_epochs_trans(const Shard &sh, const PpoCnnLearner &P, 
   PpoCnnTransArgs a;
   pc_fill_args(a, sh, P);
   a.prev_states = prev_states;
-  if (C == 5) return launch_ppo_cnn_shape<5, 5, 5, false, false, 2>(a, P.n_epochs, 1, st);
-  if (C == 4) return launch_ppo_cnn_shape<5, 5, 4, false, false, 2>(a, P.n_epochs, 1, st);
-  return launch_ppo_cnn_shape<5, 5, 8, false, false, 2>(a, P.n_epochs, 1, st);
+  return cq_dispatch(CqTwoBoardShapes{}, sh.rules_host.height, sh.rules_host.width, C, [&](auto board, auto channels) {
+    return launch_ppo_cnn_shape<decltype(board)::H, decltype(board)::W, decltype(channels)::value, false, false, 2>(a, P.n_epochs, 1, st);
+  });
 }
 
 }  // namespace sgk

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/sgk.h"
+#include "sgk_level_table.h"  // Geom<ENV>, SGK_DISPATCH_ENV
 #include "sgk_rules.h"
 
 #if defined(__HIP__)
